@@ -17,8 +17,14 @@ One rank per GPU; block b of the global batch goes to rank b mod N (static
 round-robin, no data-path collective); timing is barrier + synchronize on both
 sides, MAX over ranks; rank 0 prints ONE JSON line.
 
-After the timed headline, at N = 1 only and outside the timed region, the same
-line gains:
+A plain run sets up, warms up, times --steps steps and prints the line; the
+round trip is checked on the last timed step's outputs (exit 3 if not exact).
+--dump-outputs DIR writes what that step returned as DIR/<name>.npy (see
+dump_outputs).
+
+With --full, after the timed headline and outside the timed region, the line
+gains comp_MBps, decomp_MBps, kernel_ms and roofline (from one more, untimed
+step with per-kernel events) and, at N = 1 only:
   per_class        the headline workload one block class at a time
   value_incl_pcie  the same batch through the host-pointer entry points
                    (H2D + kernel + D2H inside the call)
@@ -248,6 +254,43 @@ def measured_traffic(dom_name, nb):
     return None, "; ".join(why[:2])
 
 
+DUMP_SAMPLE_BYTES = 24 << 20     # per sampled-bytes array of --dump-outputs (float32: 4 bytes per byte); all files < 64 MB
+
+
+def dump_outputs(path, rb):
+    """What the last timed step handed its caller, as .npy files (float64 per-block values, float32 bytes):
+    every block's encoder results (coded length, status) and decoder results (decoded length, consumed bytes,
+    final coder state, first byte, status), a CRC-32 of every block's coded stream and decoded bytes, and the
+    bytes themselves for a fixed, seeded sample of blocks (zero beyond each block's length)."""
+    import zlib
+    import numpy as np
+    nb, size, cap = rb.nb, rb.size, rb.cap
+    os.makedirs(path, exist_ok=True)
+
+    def u32(t):
+        return t.cpu().numpy().view(np.uint32).astype(np.int64)
+    coded = rb.d_out.cpu().numpy().reshape(nb, cap)
+    dec = rb.d_dec.cpu().numpy().reshape(nb, size)
+    clen, dlen = np.minimum(u32(rb.d_len), cap), np.minimum(u32(rb.d_dlen), size)
+    arrays = {
+        "coded_len": u32(rb.d_len), "encode_status": rb.d_st.cpu().numpy(),
+        "coded_crc32": [zlib.crc32(coded[i, :clen[i]]) for i in range(nb)],
+        "decoded_len": u32(rb.d_dlen), "decode_consumed": u32(rb.d_cons), "decode_final_code": u32(rb.d_code),
+        "decode_first_byte": u32(rb.d_first), "decode_status": rb.d_dst.cpu().numpy(),
+        "decoded_crc32": [zlib.crc32(dec[i, :dlen[i]]) for i in range(nb)],
+    }
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    k = max(1, min(64, nb, DUMP_SAMPLE_BYTES // (4 * cap)))
+    sample = np.sort(np.random.default_rng(0).choice(nb, k, replace=False))
+    arrays["sample_blocks"] = sample.astype(np.float64)
+    for name, buf, ln in (("coded_sample", coded, clen), ("decoded_sample", dec, dlen)):
+        cols = min(buf.shape[1], DUMP_SAMPLE_BYTES // (4 * k))
+        rows = buf[sample, :cols]
+        arrays[name] = np.where(np.arange(cols) < ln[sample, None], rows, 0).astype(np.float32)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -256,8 +299,13 @@ def main():
     ap.add_argument("--blocks", type=int, default=8192, help="blocks per GPU (weak scaling; C5 = 65536 blocks over 8 GPUs)")
     ap.add_argument("--level", type=int, default=2)
     ap.add_argument("--size", type=int, default=65536)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip per_class / value_incl_pcie / secondary (N=1 extras)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure per-kernel times and roofline and, at N = 1, per_class / "
+                         "value_incl_pcie / secondary and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0's blocks when N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip per_class / value_incl_pcie / secondary (N=1 extras)")
     ap.add_argument("--cpu-blocks-per-thread", type=int, default=32)
     ap.add_argument("--cpu-one-thread-blocks", type=int, default=48)
     ap.add_argument("--backend", default="gloo",
@@ -267,6 +315,8 @@ def main():
                     help="rehearsal on a 1-GPU box: every rank uses cuda:0 (with --backend gloo)")
     ap.add_argument("--state-budget-gib", type=float, default=0.0, help="cap the per-ctx state pool (rehearsals sharing one GPU)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Plain invocation: be the launcher.  Nothing in this process has touched a GPU (torch is not even imported), the
@@ -345,9 +395,12 @@ def main():
         rb.step(model, d_in, flags)
     sync()
     dt = time.time() - t0
-    # separate, untimed pass for per-kernel durations (event queries would add host syncs to the timed region)
-    rb.step(model, d_in, flags, record=True)
-    sync()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, rb)
+    if a.full:
+        # separate, untimed pass for per-kernel durations (event queries would add host syncs to the timed region)
+        rb.step(model, d_in, flags, record=True)
+        sync()
 
     ok = rb.ok(d_in)
     coded_bytes = rb.coded_bytes()
@@ -375,27 +428,6 @@ def main():
         ms_per_step = dt / a.steps * 1e3
         value = B_total / (dt / a.steps) / 1e6
         ratio = stats[0].item() / B_total
-        enc_ms, dec_ms = rb.enc_ms[-1], rb.dec_ms[-1]
-        roof = roofline_of(ALG_BYTES_PER_INPUT_BYTE_L.get(a.level, 195), ratio, nb, size, enc_ms, dec_ms,
-                           (rb.enc_name, rb.dec_name))
-        traffic, tnote = measured_traffic(roof["kernel"], nb)
-        roof["traffic"] = traffic
-        roof["traffic_source"] = tnote
-        if traffic:
-            # What the memory system gives THIS access pattern: the traffic is random 64-byte lines (16 bytes used of each) plus
-            # the streaming clear of the tables.  tools/micro/linerate.hip on MI355X (profiles/r03_linerate.txt): 48.2-48.7 G
-            # random lines/s read-only (3.1 TB/s), 25.3 G lines/s read + written back (50.6 G transfers/s), flat over
-            # occupancy and loads in flight; the clear runs at 6.9 TB/s (tools/init_time.py: 14.7-15.3 ms per launch).
-            clear_bytes = float(ctx.last_slots) * model.state_bytes if not ctx.last_line_store else 0.0
-            clear_ms = clear_bytes / 6.9e12 * 1e3
-            dom_ms = max(enc_ms, dec_ms)
-            glines = (traffic - clear_bytes) / 64.0 / ((dom_ms - clear_ms) * 1e-3) / 1e9
-            roof["random_lines"] = {"ceiling_G_per_s": RANDOM_LINE_CEILING_G, "achieved_G_per_s": round(glines, 2),
-                                    "frac": round(glines / RANDOM_LINE_CEILING_G, 4), "clear_bytes": int(clear_bytes),
-                                    "clear_ms_at_6.9TBps": round(clear_ms, 2),
-                                    "what": "(traffic - table clear) / 64 B over (kernel time - clear time), against the chip's measured "
-                                            "rate for random 64-byte lines (profiles/r03_linerate.txt)"}
-        roof["cycles_per_coded_bit_at_2.4GHz"] = round(max(enc_ms, dec_ms) * 1e-3 * 2.4e9 / ((size + 1) * 8), 1)
         res = {
             "metric": "MB/s (comp+decomp) on level-2 64KiB blocks", "value": round(value, 2), "unit": "MB/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 3),
@@ -409,19 +441,41 @@ def main():
                        "blocks_per_gpu": nb, "block_bytes": size, "level": a.level,
                        "parallelism": "block b -> gpu b mod %d, no collective" % world},
             "value_definition": "device-resident: inputs and outputs in HBM when the timed region starts and ends; value_incl_pcie "
-                                "(N = 1) is SURVEY 8(d)'s t, with H2D/D2H inside the calls",
+                                "(--full, N = 1) is SURVEY 8(d)'s t, with H2D/D2H inside the calls",
             "backend": a.backend if world > 1 else None,
             "roundtrip_bit_exact": all_ok, "ratio": round(ratio, 4),
             "coded_bytes": int(stats[0].item()),
-            "comp_MBps": round(nb * size / (enc_ms * 1e-3) / 1e6, 1),
-            "decomp_MBps": round(nb * size / (dec_ms * 1e-3) / 1e6, 1),
-            "kernel_ms": {rb.enc_name: round(enc_ms, 3), rb.dec_name: round(dec_ms, 3)},
             "resident_blocks": ctx.last_slots,
             "devices": devices,
-            "roofline": roof,
         }
+        if a.full:
+            enc_ms, dec_ms = rb.enc_ms[-1], rb.dec_ms[-1]
+            roof = roofline_of(ALG_BYTES_PER_INPUT_BYTE_L.get(a.level, 195), ratio, nb, size, enc_ms, dec_ms,
+                               (rb.enc_name, rb.dec_name))
+            traffic, tnote = measured_traffic(roof["kernel"], nb)
+            roof["traffic"] = traffic
+            roof["traffic_source"] = tnote
+            if traffic:
+                # What the memory system gives THIS access pattern: the traffic is random 64-byte lines (16 bytes used of each) plus
+                # the streaming clear of the tables.  tools/micro/linerate.hip on MI355X (profiles/r03_linerate.txt): 48.2-48.7 G
+                # random lines/s read-only (3.1 TB/s), 25.3 G lines/s read + written back (50.6 G transfers/s), flat over
+                # occupancy and loads in flight; the clear runs at 6.9 TB/s (tools/init_time.py: 14.7-15.3 ms per launch).
+                clear_bytes = float(ctx.last_slots) * model.state_bytes if not ctx.last_line_store else 0.0
+                clear_ms = clear_bytes / 6.9e12 * 1e3
+                dom_ms = max(enc_ms, dec_ms)
+                glines = (traffic - clear_bytes) / 64.0 / ((dom_ms - clear_ms) * 1e-3) / 1e9
+                roof["random_lines"] = {"ceiling_G_per_s": RANDOM_LINE_CEILING_G, "achieved_G_per_s": round(glines, 2),
+                                        "frac": round(glines / RANDOM_LINE_CEILING_G, 4), "clear_bytes": int(clear_bytes),
+                                        "clear_ms_at_6.9TBps": round(clear_ms, 2),
+                                        "what": "(traffic - table clear) / 64 B over (kernel time - clear time), against the chip's measured "
+                                                "rate for random 64-byte lines (profiles/r03_linerate.txt)"}
+            roof["cycles_per_coded_bit_at_2.4GHz"] = round(max(enc_ms, dec_ms) * 1e-3 * 2.4e9 / ((size + 1) * 8), 1)
+            res.update({"comp_MBps": round(nb * size / (enc_ms * 1e-3) / 1e6, 1),
+                        "decomp_MBps": round(nb * size / (dec_ms * 1e-3) / 1e6, 1),
+                        "kernel_ms": {rb.enc_name: round(enc_ms, 3), rb.dec_name: round(dec_ms, 3)},
+                        "roofline": roof})
 
-    if rank == 0 and world == 1 and not a.no_secondary:
+    if rank == 0 and world == 1 and a.full and not a.no_secondary:
         # Every extra below is optional: a failure there (say, no room for the pinned buffers) is recorded in the line,
         # it never costs the headline.
         extras_failed = {}
@@ -534,7 +588,7 @@ def main():
             res["extras_failed"] = extras_failed
 
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(a.level, size, host, a.cpu_blocks_per_thread, a.cpu_one_thread_blocks)
         print(json.dumps(res), flush=True)
     if world > 1:

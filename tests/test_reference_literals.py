@@ -31,22 +31,44 @@ def test_fixture_is_complete():
     assert REF["compsize"] == [0, 2, 3, 2, 3, 4, 6, 6, 3, 5] and len(REF["block_locator"]) == 13
 
 
-def test_fixture_is_what_the_reference_holds_now():
-    """Where the reference is on disk (the build container), the committed fixture must be what the extractor reads today."""
-    if not os.path.isdir("/root/reference/zpaq"):
-        pytest.skip("the reference is not on this machine (GPU box): the committed fixture stands")
+def _v_literals():
+    """The fixture written back as V literals of the shapes the extractor parses (const arrays with u8()/int() casts and
+    hex numbers, the level match, one CompressionLevel function per level), with comments holding `]` and `}` that
+    strip_comments must remove.  The reference itself is not part of the repository, so the extractor is held to
+    this text."""
+    def arr(name, vals):
+        items = ",\n\t".join(("u8(%d)" % v if i % 3 == 0 else "0x%x" % v if i % 3 == 1 else "int(%d)" % v)
+                             for i, v in enumerate(vals))
+        return "// %s[0] ends ] here }\nconst %s = [\n\t%s,\n]\n\n" % (name, name, items)
+    lv = sorted(REF["levels"].items())
+    text = arr("state_table_data", REF["state_table_data"]) + arr("dt_table", REF["dt_table"])
+    text += arr("compsize", REF["compsize"]) + arr("zpaq_block_locator", REF["block_locator"])
+    text += "pub fn get_compression_level(level int) CompressionLevel {\n\treturn match level {\n"
+    text += "".join("\t\t%s { %s() } // } ]\n" % (k, v["function"]) for k, v in lv)
+    text += "\t\telse { %s() }\n\t}\n}\n\n" % lv[2][1]["function"]
+    for k, v in lv:
+        text += ("fn %s() CompressionLevel {\n\treturn CompressionLevel{\n\t\tname: '%s'\n\t\thh: %d\n\t\thm: %d\n"
+                 "\t\thcomp: [%s] // ]\n\t}\n}\n\n" % (v["function"], v["name"], v["hh"], v["hm"],
+                                                       ", ".join("u8(%d)" % b for b in v["hcomp"])))
+    return text
+
+
+def test_extractor_reads_the_fixture_back_from_v_literals():
+    """tests/golden/make_reference_literals.py wrote the fixture from the reference's V literals; its parser must
+    return every value of the fixture from V text of those shapes."""
     sys.path.insert(0, os.path.join(HERE, "golden"))
     import make_reference_literals as M
-    z = "/root/reference/zpaq"
-
-    def read(fn):
-        with open(os.path.join(z, fn), encoding="utf-8") as f:
-            return M.strip_comments(f.read())
-    assert M.const_array(read("statetable.v"), "state_table_data") == REF["state_table_data"]
-    assert M.const_array(read("predictor.v"), "dt_table") == REF["dt_table"]
-    lv = read("levels.v")
-    for k, fn in M.level_functions(lv).items():
-        assert M.level_literal(lv, fn)["hcomp"] == REF["levels"][str(k)]["hcomp"]
+    text = M.strip_comments(_v_literals())
+    assert M.const_array(text, "state_table_data") == REF["state_table_data"]
+    assert M.const_array(text, "dt_table") == REF["dt_table"]
+    assert M.const_array(text, "compsize") == REF["compsize"]
+    assert M.const_array(text, "zpaq_block_locator") == REF["block_locator"]
+    fns = M.level_functions(text)
+    assert sorted(fns) == [0, 1, 2, 3, 4, 5]
+    for k, fn in fns.items():
+        want = REF["levels"][str(k)]
+        assert fn == want["function"]
+        assert M.level_literal(text, fn) == {key: want[key] for key in ("name", "hcomp", "hh", "hm")}
 
 
 # ---------------------------------------------------------------- the C oracle

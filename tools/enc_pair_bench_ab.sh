@@ -4,5 +4,5 @@
 out=$1
 for o in 0 60cd1 0 60cd1; do
   echo "== ZPQ_ENC_SPLIT=$o" >> $out
-  ZPQ_ENC_SPLIT=$o python bench.py --no-secondary --no-cpu-baseline --steps 5 --warmup 1 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['kernel_ms'])" >> $out || exit 1
+  ZPQ_ENC_SPLIT=$o python bench.py --full --no-secondary --no-cpu-baseline --steps 5 --warmup 1 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['kernel_ms'])" >> $out || exit 1
 done

@@ -1,10 +1,10 @@
 """Aggregate rocprofv3 --pmc counter CSVs (one pass per counter group, as the gfx950 guide prescribes) into the
 JSON files bench.py and DESIGN.md cite.  Usage on the GPU box, from /tmp:
-  rocprofv3 --pmc FETCH_SIZE -d OUT/fetch -o f --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline
-  rocprofv3 --pmc WRITE_SIZE -d OUT/write -o w --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline
+  rocprofv3 --pmc FETCH_SIZE -d OUT/fetch -o f --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
+  rocprofv3 --pmc WRITE_SIZE -d OUT/write -o w --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
   rocprofv3 --pmc SQ_... (two passes)
   python3 tools/pmc_collect.py OUT profiles/r01
-bench.py --steps 1 --warmup 0 launches every kernel twice (timed step + per-kernel timing step)."""
+bench.py --full --steps 1 --warmup 0 launches every kernel twice (timed step + per-kernel timing step)."""
 import collections, csv, glob, hashlib, json, os, subprocess, sys
 src, dst = sys.argv[1], sys.argv[2]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,7 +46,7 @@ if pmc:
     pmc["_blocks_per_launch"] = 8192
     pmc["_kernel_src_sha"] = kernel_src_sha()
     pmc["_commit"] = commit()
-    pmc["_note"] = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `python3 bench.py --steps 1 --warmup 0 "
+    pmc["_note"] = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `python3 bench.py --full --steps 1 --warmup 0 "
                     "--no-cpu-baseline` (level 2, 8192 x 64 KiB blocks per launch), aggregated by tools/pmc_collect.py. Unit: KB (x1024). "
                     "MI355X_MICROARCH.md: on gfx950 FETCH_SIZE halves WIDE COALESCED 16 B/lane streams (128-B requests tallied at 64 B); "
                     "this kernel's reads are random 16-B rows out of 64-B lines, an uncalibrated pattern, so both the raw sum "

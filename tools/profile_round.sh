@@ -5,7 +5,7 @@
 out=$1; export ZPQ_COMMIT=$2
 mkdir -p $out
 export TMPDIR=/tmp
-B="python3 bench.py --no-secondary --no-cpu-baseline"
+B="python3 bench.py --full --no-secondary --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats -d $out/kt -o kt --output-format csv -- $B --steps 5 --warmup 1 > $out/kt.log 2>&1
 P1="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS"
 P2="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_BRANCH SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"
