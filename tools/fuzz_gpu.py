@@ -1,7 +1,7 @@
 """Randomised parity soak on the GPU box: ragged batches of random shape through the batch entry points (whatever
 kernels the plan picks: k_pipe / k_chain / k_rows / k_generic, dense tables or the line store, one launch or several
 rounds of slot reuse), every coded stream compared with the CPU oracle, every block decoded back.
-Usage: python tools/fuzz_gpu.py [--seconds 300] [--seed 1]; prints one line per batch and a summary; exit code 1 on
+Usage: python tools/fuzz_gpu.py [--seconds 300] [--seed 1] [--general | --chains]; prints one line per batch and a summary; exit code 1 on
 the first mismatch (the offending batch is described so that it can be replayed with --seed/--only)."""
 import argparse
 import os
@@ -18,6 +18,7 @@ import __graft_entry__ as ge  # noqa: E402
 import oracle_lib as O  # noqa: E402
 import workload as W  # noqa: E402
 from inputs import C4B  # noqa: E402
+import chain_models as CM  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--seconds", type=float, default=300)
@@ -26,6 +27,8 @@ ap.add_argument("--only", type=int, default=-1, help="run only batch number N of
 ap.add_argument("--general", action="store_true", help="general models: random mixes of the nine component types (inputs = earlier "
                 "components, hash-chain program), C4b, levels 2-3 as general models -- the wave-per-component encoder k_gpipe in its "
                 "byte-batched and bit-serial forms, decoded back by k_rows")
+ap.add_argument("--chains", action="store_true", help="random chain models (tests/chain_models.py: any chain length, table sizes, "
+                "hh / hm, program and MIX2) -- the specialised and the runtime-loop chain kernels; the summary counts the routes")
 ap.add_argument("--levels", default="", help="comma-separated levels to draw from instead of the default mix (e.g. 3,4: the round-4 decoders)")
 a = ap.parse_args()
 
@@ -35,6 +38,7 @@ L = z.lib()
 rnd = random.Random(a.seed)
 t_end = time.time() + a.seconds
 names = {}
+routes = {}
 nbatch = nblocks = nbytes = 0
 
 
@@ -108,14 +112,23 @@ while time.time() < t_end:
     if a.general:
         which = r.choice(["rnd", "rnd", "rnd", "c4b", "c4b", 2, 3])
         lanes_flag = z.FLAG_LANES if which in (2, 3) else 0
+    if a.chains:
+        which = "chain"
     if which == "rnd":
         header, comps = random_model(r)
         which = "rnd%s" % comps
+    elif which == "chain":
+        header = CM.random_chain(r, big=True)
     else:
         header = C4B if which == "c4b" else O.level_header(which)
     model = z.Model(header=header)
+    rclass = CM.route_class(CM.route(z, model)) if which == "chain" else None
+    if rclass:
+        which = "chain %s %s" % (rclass, header.hex())
     nb = r.choice([1, 2, 5, 11, 12, 13, 16, 17, 31, 33, 64, 100, 150])
     if which in (4, 5, "c4b") and not a.general:
+        nb = min(nb, 33)
+    if rclass and max(CM.table_bits(header)) >= 18:         # (the oracle clears 64 << bits bytes per table and block)
         nb = min(nb, 33)
     maxlen = r.choice([0, 1, 7, 64, 300, 2000, 9000])
     blocks = [make(r.randrange(6), r.randint(0, maxlen) if r.random() < 0.8 else maxlen, r) for _ in range(nb)]
@@ -127,9 +140,13 @@ while time.time() < t_end:
         blocks = [make(r.randrange(6), r.randint(0, maxlen) if r.random() < 0.8 else maxlen, r) for _ in range(nb)]
         if r.random() < 0.3:
             env["ZPQ_GPIPE_BATCH"] = "0"
-    if which in (1, 2, 3, 4) and r.random() < 0.3:
+    if rclass and r.random() < 0.15:
+        env["ZPQ_DEC_HYP16" if r.random() < 0.5 else "ZPQ_ENC_PIPE"] = "0"
+    if rclass and r.random() < 0.15:
+        env["ZPQ_DEC_PIPE"] = "1"
+    if (which in (1, 2, 3, 4) or rclass) and r.random() < 0.3:
         env["ZPQ_SPARSE_FORCE_LOG2"] = str(r.choice([12, 13, 15]))
-    elif which in (1, 2, 3, 4) and r.random() < 0.3:
+    elif (which in (1, 2, 3, 4) or rclass) and r.random() < 0.3:
         env["ZPQ_SPARSE_MODE"] = r.choice(["never", "always"])
     if which in (3, 4) and r.random() < 0.15:
         env["ZPQ_DEC_HYP16"] = "0"                          # (the eight-lane decoders stay covered)
@@ -170,8 +187,11 @@ while time.time() < t_end:
         if budget:
             L.zpq_ctx_set_state_budget(ctx.h, 150 << 30)
     names[(ename, dname)] = names.get((ename, dname), 0) + 1
+    if rclass:
+        routes[rclass] = routes.get(rclass, 0) + 1
     nblocks += nb
     nbytes += sum(len(b) for b in blocks)
     if nbatch % 20 == 0:
         print("%d batches, %d blocks, %.1f MB ok; last: %s -> %s/%s slots %d" % (nbatch, nblocks, nbytes / 1e6, desc, ename, dname, slots), flush=True)
-print("DONE: %d batches, %d blocks, %.1f MB, all equal to the oracle; kernels used: %s" % (nbatch, nblocks, nbytes / 1e6, names))
+print("DONE: %d batches, %d blocks, %.1f MB, all equal to the oracle; kernels used: %s%s" % (
+    nbatch, nblocks, nbytes / 1e6, names, "; chain routes: %s" % dict(sorted(routes.items())) if routes else ""))

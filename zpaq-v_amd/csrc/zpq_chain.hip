@@ -1669,6 +1669,18 @@ extern "C" int zpq_chain_blocks_per_wg(const DModel *M)
     return build_cfg(M, &cfg) ? cfg.blocks_per_wg : 0;
 }
 
+// (internal, for the tests: build_cfg's verdict on a model -- which k_chain instantiation its batches get, which the
+// kernel name alone does not tell.  out = n, nisse_end, has_mix2, nch_spec (0 = runtime loops), g, vm_kind,
+// blocks_per_wg, sparse.  0 = not a chain model: the lanes / generic kernels take it.)
+extern "C" int zpq_chain_route(const DModel *M, int32_t out[8])
+{
+    Cfg cfg;
+    if (!M || !build_cfg(M, &cfg)) return 0;
+    const int32_t v[8] = {cfg.n, cfg.nisse_end, cfg.has_mix2, cfg.nch_spec, cfg.g, cfg.vm_kind, cfg.blocks_per_wg, cfg.sparse};
+    if (out) memcpy(out, v, sizeof v);
+    return 1;
+}
+
 // Blocks per workgroup for a batch: as few as keeps every CU busy (each wave then has a SIMD
 // to itself), never more than the LDS allows; a multiple of the blocks one wave carries.
 static int plan_blocks_per_wg(const Cfg &cfg, int nblocks, int cus)
