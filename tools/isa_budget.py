@@ -97,7 +97,7 @@ def source_ranges(src_path):
                ("hyp: bit broadcast", "y = bcast_down(y);", hyp0),
                ("hyp: commit / take over", "// ---- commit / take over", hyp0),
                ("hyp: next state into the row, c8, slot", "// next bit-history state into the row (statetable.v:75-84), with the decoded bit", hyp0),
-               ("hyp: row requests (HYP4 / last-bit)", "if (HYP4 && bit == 6) {", hyp0)]
+               ("hyp: row requests (last-bit)", "if (K == 2) {", hyp0)]
         for role, pat, st in sub:
             ln = find(pat, st)
             if ln:

@@ -1,10 +1,11 @@
 """Aggregate rocprofv3 --pmc counter CSVs (one pass per counter group, as the gfx950 guide prescribes) into the
 JSON files bench.py and DESIGN.md cite.  Usage on the GPU box, from /tmp:
-  rocprofv3 --pmc FETCH_SIZE -d OUT/fetch -o f --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
-  rocprofv3 --pmc WRITE_SIZE -d OUT/write -o w --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline
+  rocprofv3 --pmc FETCH_SIZE -d OUT/fetch -o f --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline
+  rocprofv3 --pmc WRITE_SIZE -d OUT/write -o w --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline
   rocprofv3 --pmc SQ_... (two passes)
   python3 tools/pmc_collect.py OUT profiles/r01
-bench.py --full --steps 1 --warmup 0 launches every kernel twice (timed step + per-kernel timing step)."""
+bench.py --steps 1 --warmup 0 launches the headline's two kernels and nothing else (a counter is averaged over the launches the
+pass saw); with --full it also launches the secondary configurations, whose kernels carry the same names: do not profile that."""
 import collections, csv, glob, hashlib, json, os, subprocess, sys
 src, dst = sys.argv[1], sys.argv[2]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,9 +23,9 @@ def commit():
         return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or os.environ.get("ZPQ_COMMIT", "")
     except Exception:
         return os.environ.get("ZPQ_COMMIT", "")
-LAUNCHES = 2
 enc_name = "k_chain<encode>"
 agg = collections.defaultdict(lambda: collections.defaultdict(float))
+launches = collections.defaultdict(lambda: collections.defaultdict(int))
 for f in glob.glob(os.path.join(src, "**", "*counter_collection.csv"), recursive=True):
     for r in csv.DictReader(open(f)):
         k = r["Kernel_Name"]
@@ -33,7 +34,11 @@ for f in glob.glob(os.path.join(src, "**", "*counter_collection.csv"), recursive
         role = "decode" if "k_chain<true" in k else "encode"
         if role == "encode":
             enc_name = ("k_pipe2<encode>" if "k_pipe2" in k else "k_pipe<encode>") if "k_pipe" in k else "k_chain<encode>"
-        agg[role][r["Counter_Name"]] += float(r["Counter_Value"]) / LAUNCHES
+        agg[role][r["Counter_Name"]] += float(r["Counter_Value"])
+        launches[role][r["Counter_Name"]] += 1
+for role in agg:
+    for name in agg[role]:
+        agg[role][name] /= launches[role][name]
 pmc = {}
 for role in ("encode", "decode"):
     c = agg[role]
@@ -46,7 +51,7 @@ if pmc:
     pmc["_blocks_per_launch"] = 8192
     pmc["_kernel_src_sha"] = kernel_src_sha()
     pmc["_commit"] = commit()
-    pmc["_note"] = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `python3 bench.py --full --steps 1 --warmup 0 "
+    pmc["_note"] = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes of `python3 bench.py --steps 1 --warmup 0 "
                     "--no-cpu-baseline` (level 2, 8192 x 64 KiB blocks per launch), aggregated by tools/pmc_collect.py. Unit: KB (x1024). "
                     "MI355X_MICROARCH.md: on gfx950 FETCH_SIZE halves WIDE COALESCED 16 B/lane streams (128-B requests tallied at 64 B); "
                     "this kernel's reads are random 16-B rows out of 64-B lines, an uncalibrated pattern, so both the raw sum "

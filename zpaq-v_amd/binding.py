@@ -48,7 +48,7 @@ class ZpqError(RuntimeError):
 
 
 def lib_path():
-    # ZPQ_LIB_PATH: another build of the same library (kernel experiments, tools/variants.sh)
+    # ZPQ_LIB_PATH: another build of the same library (kernel experiments, tools/variant.sh)
     return os.environ.get("ZPQ_LIB_PATH") or os.path.join(HERE, "lib", "libzpaq_hip.so")
 
 

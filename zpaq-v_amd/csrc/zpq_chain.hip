@@ -41,15 +41,8 @@
 
 // Measured on MI355X: the pipelined step wins for encode, for decode the step with
 // fewer instructions wins (both-candidate speculation was slower every time it was tried).
-#ifndef ZPQ_CHAIN_G_DEFAULT
-#define ZPQ_CHAIN_G_DEFAULT 8
-#endif
-#ifndef ZPQ_CHAIN_SPEC_ENC
-#define ZPQ_CHAIN_SPEC_ENC 1
-#endif
-#ifndef ZPQ_CHAIN_SPEC_DEC
-#define ZPQ_CHAIN_SPEC_DEC 0
-#endif
+constexpr int CHAIN_G_DEFAULT = 8;            // lanes per block where the model fits (ZPQ_CHAIN_G at run time)
+constexpr bool CHAIN_SPEC_ENC = true, CHAIN_SPEC_DEC = false;
 
 namespace zpqc {
 
@@ -168,15 +161,6 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
     // 2^23, garbage on lanes that hold none is cut to the table); `cm` may be any u32
     auto stretch_of = [&](u32 cm) -> i32 {
         if constexpr (DST) return reinterpret_cast<const int16_t *>(lds)[(cm >> 8) & 32767u];
-#ifdef ZPQ_STRETCH_ENDS
-        u32 q = cm >> 8;
-        q = min(max(q, 1u), 32767u);
-        const u32 wv = s_stretch[q >> 4];
-        const u32 ei = q < 64u ? q : (q - 32704u + 64u);
-        const i32 endv = (i32)(int16_t)s_stretch[2048 + (ei & 127u)];
-        const i32 midv = (i32)(int16_t)(wv >> 16) + __popc(wv & ((2u << (q & 15u)) - 1u) & 0xFFFEu);
-        return (q < 64u || q >= 32704u) ? endv : midv;
-#else
         // The table rises by at most 1 per entry everywhere but at its last one (stretch(32767) = 2047 after 375; checked
         // exhaustively where the packing is built, zpq_model.cpp) -- and no ICM counter gets there: cminit's largest is
         // 31987 << 8 (checked there too), and an update adds (32767 - q) >> 2 to cm = 256 q + r, which cannot carry q to 32767 (that needs
@@ -184,7 +168,6 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
         // word 0's base is stretch(1), which is also the reference's stretch(0) (predictor.v:205-214).
         const u32 wv = s_stretch[(cm >> 12) & 2047u];
         return ((i32)wv >> 16) + (i32)__popc(__builtin_amdgcn_ubfe(wv, 1u, (cm >> 8) & 15u));
-#endif
     };
     const int lane = tid & 63, wave = tid >> 6;
     const int grp = lane / G, li = lane % G;
@@ -224,28 +207,8 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
     // (Dense tables without a MIX2 only: with the line store the second probe doubles tag loads and selects, and the
     //  MIX2 levels have eight tables to fetch twice -- measured slower there: level 5 505 vs 466 ms.)
     constexpr bool TWO = DEC && !SPEC && !HYP && NCH > 0 && !SP && !MIXT;
-    // Line-store decoders (levels 3-5 at scale): the two outcomes of a byte's FOURTH bit lead to neighbouring contexts, and the
-    // store places neighbouring lines in one group of four slots (see ZPQ_PREFETCH) -- so for the mid-byte boundary, and only
-    // there, both outcomes are requested when the third bit is known: one tag group and two neighbouring lines three times out
-    // of four, a whole bit step early.  (The byte boundary's two outcomes are unrelated lines: asking for both was measured
-    // slower in round 2, level 5 505 vs 466 ms.)
-    // Built in round 3, parity-green (65 GPU tests), MEASURED SLOWER at the shapes bench.py ships: level 3 x 4096 393.5 against
-    // 382.6 ms, level 4 x 4096 511.6 against 491.1, level 5 x 3072 503.0 against 477.4 -- the second set of tag and row loads,
-    // the seventeen selects and 30-60 more registers cost more than the hidden half round trip, and four neighbouring lines
-    // filling one home group push unrelated lines into the walk.  Compiled only with -DZPQ_TWOM (tools/variant.sh).
-#ifdef ZPQ_TWOM
-    constexpr bool TWOM = DEC && !SPEC && SP && NCH > 0;
-#else
-    constexpr bool TWOM = false;
-#endif
-    // The store's PLACEMENT that goes with it -- neighbouring second-nibble contexts in one group of four slots, home slot =
-    // index & 3 -- also serves the sixteen-lane two-hypothesis decoders (-DZPQ_HYP16_NBR): the two copies' mid-byte requests then
-    // read ONE tag group and two neighbouring lines instead of two unrelated pairs.  The layout lives and dies with the launch.
-#ifdef ZPQ_HYP16_NBR
-    constexpr bool NBR = TWOM || (HYP16 && SP);
-#else
-    constexpr bool NBR = TWOM;
-#endif
+    // (Line-store decoders asking for both outcomes of a byte's FOURTH bit, neighbouring lines placed in one group of four
+    //  slots: parity-green, measured slower -- EXPERIMENTS.md 4.1 `TWOM`; the placement alone at sixteen lanes: R4.3, no gain.)
     // (Requesting only the LIKELIER outcome early -- as soon as the last bit's probability is known, asking again after
     //  a wrong guess -- was measured as well: level 3 375 -> 472 ms, level 5 467 -> 557 ms.  Every speculative row read
     //  these decoders add costs more in memory latency under load than it hides; they request after the bit is known.)
@@ -261,28 +224,18 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
     // lanes without a hash table (idle, MIX2) run the same row loads against the first 64
     // bytes of the slot: no exec-masked branch around the loads (a branch join would make
     // the compiler wait for them at once and defeat the prefetch); only the store is masked
-    const u32 ht_mask = hashed ? ((C.ht_len - 16u) & cfg.dbg_ht_and) : 0u;
+    const u32 ht_mask = hashed ? C.ht_len - 16u : 0u;
     // compact line store: u32 tags[cap] (dense line index + 1, 0 = free) + 64-byte lines[cap] instead of the dense
     // table.  cap is a multiple of 4, about 1.12x the lines the largest block can touch (zpq_ctx_set_max_block_bytes).
     constexpr bool SPARSE = SP;
     const u32 sp_cap = (SPARSE && hashed) ? C.sp_cap : 0u;
     const u32 sp_groups = sp_cap >> 2;
-    const u32 sp_qbits = (SPARSE && hashed && C.ht_len >= 256u) ? (u32)(31 - __clz((int)C.ht_len)) - 8u : 0u;   // log2(lines / 4)
     u32 *sp_tags = reinterpret_cast<u32 *>(slot + C.sp_tag_off);
     // every row access of this lane is tbase + a 32-bit byte offset: the dense table, or the store's line array
     // (offsets, not pointers, so that the h0 ^ 16 / ^ 32 neighbours stay provably global addresses)
     u8 *const tbase = hashed ? (sp_cap ? slot + C.sp_line_off : slot + C.ht_off) : slot;
-    // "touched" bitmap of a dense table that is not cleared (two-hypothesis decoder; zpq_touch_layout): one bit per row.
-    // Built, parity-green and MEASURED SLOWER (level 2 decode 283.6 ms against 261 ms with the 15 ms of clearing; the code
-    // alone, switched off at run time, cost 12 ms): one more load per request in the in-order vmcnt queue, twelve selects,
-    // one more register to exchange between the copies.  Compiled only with -DZPQ_TOUCH_DEC (tools/variant.sh).
-#ifdef ZPQ_TOUCH_DEC
-    constexpr bool TOUCHC = true;
-#else
-    constexpr bool TOUCHC = false;
-#endif
-    const bool touch = TOUCHC && hashed && C.tb_off != 0;
-    u32 *const tb32 = reinterpret_cast<u32 *>(slot + (touch ? C.tb_off : 0));
+    // (A "touched" bitmap in place of clearing the dense tables: parity-green, measured slower at levels 1 and 2 --
+    //  EXPERIMENTS.md 4.1 "Zero-fill replaced by a touched bitmap" and R4.4.)
     const int sizebits = C.a + 2;
     // Packed per-block state.  ISSE weights are 20-bit two's complement (clamp512k,
     // predictor.v:228-236): t32[s] = (w0 & 0xFFFFF) | (w1 << 20), t8[s] = w1 >> 12.  An ICM entry is
@@ -526,24 +479,20 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
         // sits in its home slot, or a new line (it takes the first free slot it meets, and a new line is all
         // zero -- nothing to load), costs one memory round trip; only a line that was displaced when it
         // was claimed needs a second one for its rows, and only a full group is walked past.
-#define ZPQ_PREFETCH(A_, B_, C_, tags_, po_, chk_, key_, si_, off_, tw_, hc_, c8v_)     \
+#define ZPQ_PREFETCH(A_, B_, C_, tags_, po_, chk_, key_, si_, off_, hc_, c8v_)          \
     do {                                                                                \
         const u32 cx_ = (hc_) + 16u * (c8v_);                                           \
         chk_ = (cx_ >> sizebits) & 255u;                                                \
         const u32 h0_ = (cx_ * 16u) & ht_mask;                                          \
         u32 pox_ = SWZ ? swz_addr(h0_) : h0_;                                           \
         if (SPARSE && sp_cap) {                                                         \
-            /* the line's index with the two lowest bits moved to the top (neighbouring second-nibble contexts = */ \
-            /* neighbouring indices); four neighbouring indices share a home group, index & 3 is the home slot     */ \
-            const u32 tl_ = NBR ? (((h0_ >> 6) & 3u) << sp_qbits) | (h0_ >> 8) : (h0_ >> 6); \
-            key_ = tl_ + 1u;                                                            \
-            si_ = NBR ? 4u * __umulhi((tl_ >> 2) * 0x9E3779B1u, sp_groups) + (tl_ & 3u) : __umulhi(key_ * 0x9E3779B1u, sp_cap); \
+            key_ = (h0_ >> 6) + 1u;                                                     \
+            si_ = __umulhi(key_ * 0x9E3779B1u, sp_cap);                                 \
             off_ = h0_ & 48u;                                                           \
             tags_ = *reinterpret_cast<const u32x4 *>(sp_tags + (si_ & ~3u));            \
             pox_ = (si_ << 6) + off_;                                                   \
         }                                                                               \
         po_ = pox_;                                                                     \
-        if (HYP && TOUCHC) tw_ = tb32[touch ? (pox_ >> 9) : 0u];   /* the line's four "touched" bits (32 rows per word) */ \
         ZPQ_LOAD_ROWS(A_, B_, C_, pox_);                                                \
     } while (0)
         // Two-hypothesis decode: inside this launch a table's 64-byte lines are TRANSPOSED -- line (h0 >> 6) & 3 of every
@@ -563,9 +512,8 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             return swz_q ? t : h0;
         };
         auto load_rows = [&](const u32 po) { ZPQ_LOAD_ROWS(nA, nB, nC, po); };
-        u32 n_tw = 0xFFFFFFFFu, a_tw = 0xFFFFFFFFu;        // "touched" words of the requests in flight
-        auto prefetch_rows = [&](const u32 hc, const u32 c8v) { ZPQ_PREFETCH(nA, nB, nC, n_tags, n_po, n_chk, n_key, n_si, n_off, n_tw, hc, c8v); };
-        auto prefetch_alt = [&](const u32 hc, const u32 c8v) { ZPQ_PREFETCH(aA, aB, aC, a_tags, a_po, a_chk, a_key, a_si, a_off, a_tw, hc, c8v); };
+        auto prefetch_rows = [&](const u32 hc, const u32 c8v) { ZPQ_PREFETCH(nA, nB, nC, n_tags, n_po, n_chk, n_key, n_si, n_off, hc, c8v); };
+        auto prefetch_alt = [&](const u32 hc, const u32 c8v) { ZPQ_PREFETCH(aA, aB, aC, a_tags, a_po, a_chk, a_key, a_si, a_off, hc, c8v); };
         // Consume the rows requested one nibble ago, THEN write the finished row back (so that
         // the wait for the loads does not also wait for a just-issued store), then the caller
         // requests the next nibble's rows.  The finished row is forwarded from registers if it
@@ -574,45 +522,22 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
         // (mov_dpp, not update_dpp(old = v, ...): every lane has a source under this permutation, and with no `old` operand
         //  tied to the destination the compiler needs no copy of v in front of the v_mov_b32_dpp)
         auto xchg = [&](const u32 v) -> u32 {
-#ifdef ZPQ_DPP_OLD
-            return (u32)__builtin_amdgcn_update_dpp((i32)v, (i32)v, 0xB1 /*quad_perm:[1,0,3,2]*/, 0xf, 0xf, false);
-#else
             return (u32)__builtin_amdgcn_mov_dpp((i32)v, 0xB1 /*quad_perm:[1,0,3,2]*/, 0xf, 0xf, true);
-#endif
         };
         const bool wr_lane = hashed && (!HYP || hyp == 0);  // this lane writes finished rows back
         const bool mix_lane = ctype == ZT_MIX2;
         bool row_mine = true;                              // this copy requested the rows of the nibble that really follows
-        // Two-hypothesis decode, a byte's SECOND nibble: its 16 possible contexts are hctx + 16 * (16..31) (predictor.v:558-560),
-        // i.e. -- in the transposed layout above -- 16 neighbouring lines.  So the request need not wait for the first nibble's
-        // third bit: when the SECOND bit is known each copy asks for the two lines of ITS outcome of the third bit (both outcomes
-        // of the fourth: neighbouring lines, half of the time one 128-byte block), two whole bit steps before they are needed --
-        // the HBM round trip (~2000 cycles under this load, tools/micro/rowlat.hip) then hides completely instead of by half.
-        // Four lines per table and byte instead of two, but four NEIGHBOURING ones: asking two steps early for four lines 256
-        // bytes apart was measured slower in round 2 (321 vs 267 ms).
-        // Round 4 (EXPERIMENTS.md R4.11): on the dieted kernel the early request buys nothing any more -- level 2 x 8192, processes
-        // balanced over a box's fast and slow places: 235.3-236.9 ms without against 235.7-239.4 with -- and it reads a third more
-        // lines (4 instead of 2 per table for a byte's second nibble).  Off by default; -DZPQ_HYP4 (tools/variant.sh) brings it back.
-#ifndef ZPQ_HYP4
-        constexpr bool HYP4 = false;
-#else
-#ifdef ZPQ_HYP4_L1
-        constexpr bool HYP4 = HYP && SWZ;
-#else
-        constexpr bool HYP4 = HYP && SWZ && NCH == 3;         // (level 1, one hashed table of 32 MiB beside a small one: measured 272 vs 269 ms)
-#endif
-#endif
-        auto take_prefetched = [&](const bool have_prev, auto midc) {
-            constexpr bool MID = decltype(midc)::value;        // the rows of a byte's second nibble
+        // (Asking for a byte's second-nibble rows two bit steps early -- four neighbouring lines per table instead of two: buys
+        //  nothing on the dieted kernel and reads a third more lines -- EXPERIMENTS.md 4.1 `HYP4` and R4.11.)
+        auto take_prefetched = [&](const bool have_prev) {
             bool claim = false;
             u32 claim_si = 0;
-            if (TWO || ((HYP4 || TWOM) && MID)) {              // (selects, not a branch: both requests are waited for here anyway)
+            if (TWO) {                                         // (selects, not a branch: both requests are waited for here anyway)
                 auto sel4 = [](const bool c, const u32x4 a, const u32x4 b) -> u32x4 {
                     return u32x4{c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w};
                 };
                 nA = sel4(sel_alt, aA, nA); nB = sel4(sel_alt, aB, nB); nC = sel4(sel_alt, aC, nC);
                 n_po = sel_alt ? a_po : n_po; n_chk = sel_alt ? a_chk : n_chk;
-                if (HYP && TOUCHC) n_tw = sel_alt ? a_tw : n_tw;
                 if (SPARSE) {
                     n_tags = sel4(sel_alt, a_tags, n_tags);
                     n_key = sel_alt ? a_key : n_key; n_si = sel_alt ? a_si : n_si; n_off = sel_alt ? a_off : n_off;
@@ -663,18 +588,6 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
                     load_rows(n_po);
                 }
             }
-            u32 tw_line = 0xFFFFFFFFu;
-            if constexpr (HYP && TOUCHC) {
-                // a row of a table that is never cleared counts only once it has been written: untouched rows read as zeros
-                tw_line = touch ? n_tw : 0xFFFFFFFFu;
-                const u32 rb = (n_po >> 4) & 31u;
-                const u32x4 z4 = {0, 0, 0, 0};
-                const bool ta = ((tw_line >> rb) & 1u) != 0, tb = ((tw_line >> (rb ^ 1u)) & 1u) != 0, tc = ((tw_line >> (rb ^ 2u)) & 1u) != 0;
-                nA = u32x4{ta ? nA.x : 0u, ta ? nA.y : 0u, ta ? nA.z : 0u, ta ? nA.w : 0u};
-                nB = u32x4{tb ? nB.x : 0u, tb ? nB.y : 0u, tb ? nB.z : 0u, tb ? nB.w : 0u};
-                nC = u32x4{tc ? nC.x : 0u, tc ? nC.y : 0u, tc ? nC.z : 0u, tc ? nC.w : 0u};
-                (void)z4;
-            }
             const u32x4 Rp = {X.r0, X.r1, X.r2, X.r3};
             const u32 poff = roff;
             const bool fa = have_prev && n_po == poff;
@@ -687,7 +600,6 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
                 const u32 x0 = xchg(X.r0), x1 = xchg(X.r1), x2 = xchg(X.r2), x3 = xchg(X.r3), xo = xchg(roff);
                 X.r0 = row_mine ? X.r0 : x0; X.r1 = row_mine ? X.r1 : x1; X.r2 = row_mine ? X.r2 : x2; X.r3 = row_mine ? X.r3 : x3;
                 roff = row_mine ? roff : xo;
-                if (TOUCHC) { const u32 xt = xchg(tw_line); tw_line = row_mine ? tw_line : xt; }
                 if constexpr (SPARSE) {
                     // the store's bookkeeping lives on both copies and must agree: what the resolving copy counted and found
                     const u32 xc = xchg(sp_claims), xs = xchg((u32)status), xf = xchg(sp_full ? 1u : 0u);
@@ -713,12 +625,6 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             // (one predicate, the lane's part of it computed once: `have_prev && hashed && ...` as written became a twenty-instruction
             //  maze of exec-mask moves around one store)
             if (have_prev & wr_lane) *reinterpret_cast<u32x4 *>(tbase + poff2) = Rp;   // (both copies hold the same row: copy 0 writes)
-            if constexpr (HYP && TOUCHC) {
-                // the row this nibble works on counts as written from now on (it is stored when the nibble ends; until then a
-                // request that meets it takes it from the registers)
-                const u32 nbit = 1u << ((roff >> 4) & 31u);
-                if (touch && hyp == 0 && (tw_line & nbit) == 0u) tb32[roff >> 9] = tw_line | nbit;
-            }
 #endif
         };
         // ZPAQL.run(byte) + h[] copy (predictor.v:809-816) -> this lane's next context hash
@@ -883,11 +789,8 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
         // (mixs_arrive, behind take_prefetched) copy 0 writes the ended nibble's candidates back, the copy that was right
         // parks its loaded values in LDS -- an entry that was also a candidate of the nibble that just ended is taken from
         // LDS, where its trained value sits (its load went out before that nibble's last training and write-back) -- and both
-        // copies adopt its addresses.  ZPQ_MIXW_SPEC=0 at build time: ask after the bit, as the one-copy decoders do.
-#ifndef ZPQ_MIXW_SPEC
-#define ZPQ_MIXW_SPEC 1
-#endif
-        constexpr bool MIXS = HYP && MIXT && (ZPQ_MIXW_SPEC != 0);
+        // copies adopt its addresses.
+        constexpr bool MIXS = HYP && MIXT;
         u32 ms_cur[2] = {0, 0}, ms_new[2] = {0, 0}, ms_ld[2] = {0, 0};
         u32 ms_hm = 0, ms_prefix = 1;                      // what THIS copy's request in flight was derived from
         u32 hctx_mix = 0, hn_spec_mix = 0, hnext_mix = 0;  // the MIX2's context hash: this byte / next byte under this copy's outcome / next byte
@@ -1074,7 +977,7 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
                 // the nibble's last bit is known: request the next nibble's rows now, so that their
                 // latency overlaps this bit's update work (contexts: predictor.v:558-560,809-816)
                 const u32 c8n = (X.c8 << 1) | (u32)y;
-                if (bit == 4) { if (TWOM) sel_alt = y != 0; else prefetch_rows(hctx, c8n); }
+                if (bit == 4) prefetch_rows(hctx, c8n);
                 else { hnext_dec = run_vm(c8n - 256u); prefetch_rows(hnext_dec, 1u); }
             }
             if (DEC && K == 3 && TWO) {
@@ -1159,11 +1062,6 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             else { X.r3 = (X.slot & 4u) ? ins : X.r3; X.r2 = (X.slot & 4u) ? X.r2 : ins; }
             X.c8 = (X.c8 << 1) | (u32)y;
             X.slot = (K == 3) ? 1u : (X.slot * 2u + (u32)y);
-            if (TWOM && bit == 5) {
-                const u32 c8n = X.c8 << 1;                       // (mid-byte: both values of the fourth bit, see TWOM)
-                prefetch_alt(hctx, c8n | 1u);
-                prefetch_rows(hctx, c8n);
-            }
             if (TWO && K == 2) {
                 // three bits of the nibble are known: request the next nibble's rows for both values of the fourth
                 const u32 c8n = X.c8 << 1;
@@ -1192,14 +1090,10 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             R.p = is_icm ? icm_st(v, b) : 0; R.pin = 0; R.pj = 0; R.pk = 0; R.wmix = 0;
 #pragma unroll
             for (int i = 1; i < (NCH ? NCH : 1); i++) {
-#ifdef ZPQ_DPP_OLD
-                const i32 pv = __builtin_amdgcn_update_dpp(R.p, R.p, 0x112 /*row_shr:2: the same copy of the component below*/, 0xf, 0xf, false);
-#else
                 // (no `old` operand tied to the destination: no copy in front of the v_mov_b32_dpp.  Lanes 0 and 1 of a DPP row have
                 //  no lane two below and read 0; they, and lanes 8 and 9 where a row carries two blocks of eight, are the ICM's
                 //  copies, which use no input prediction)
                 const i32 pv = __builtin_amdgcn_mov_dpp(R.p, 0x112 /*row_shr:2: the same copy of the component below*/, 0xf, 0xf, true);
-#endif
                 const i32 pn = clamp2k((__mul24(w0c, pv) + (w1c << 6)) >> 16);
                 R.p = (lc == i) ? pn : R.p;
             }
@@ -1216,22 +1110,8 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             }
             return R;
         };
-        // AHEAD (round 4): inside a nibble each copy also runs the NEXT bit's chain and squash lookup for its outcome of this
-        // bit -- its next state's entry with its own training forwarded is all the chain needs -- BEFORE the coder resolves
-        // this bit.  The copy that was right hands (input, squash, MIX2 operands) over with the entry, and the next step starts
-        // at its coder: the chain's DPP hops and the squash's LDS round trip leave the bit-to-bit critical path (they were
-        // ~200 cycles of the ~340 a bit step spends waiting).  The first bit of a nibble has a new row and predicts as before.
-        // MEASURED SLOWER on every level (same box, alternating runs, profiles/r04_ahead_ab.txt): level 2 x 8192 272-274 against
-        // 257.7-257.9 ms, level 1 282 against 261, level 3 360 against 337, level 4 484 against 455-459.  The bit step's one LDS
-        // round trip does not go away -- the next state's entry and the ICM's stretch of its trained counter (needed when the state
-        // repeats) must have arrived before the early chain can start, where they used to arrive behind the coder -- and the
-        // hand-over grows by two to five registers.  Parity-green (the whole GPU suite ran on it).  Compiled only with -DZPQ_AHEAD.
-#ifdef ZPQ_AHEAD
-        constexpr bool AHEAD = HYP;
-#else
-        constexpr bool AHEAD = false;
-#endif
-        i32 a_pin = 0, a_sq = 0, a_pj = 0, a_pk = 0, a_wmix = 0;
+        // (Each copy also running the NEXT bit's chain and squash lookup before the coder resolves this bit: parity-green, measured
+        //  slower on every level -- EXPERIMENTS.md R4.5 `AHEAD`, profiles/r04_ahead_ab.txt.)
         auto bitstep_hyp = [&](auto kc, auto nbc) {
             constexpr int K = decltype(kc)::value;
             constexpr int bit = (decltype(nbc)::value ? 3 : 7) - K;
@@ -1240,14 +1120,9 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             const u32 cmv = cur_v & 0x7FFFFFu;
             const i32 w0 = ((i32)(cur_v << 12)) >> 12;
             const i32 w1 = (i32)(((u32)cur_b << 12) | (cur_v >> 20));
-            i32 pin, pj, pk, wmix, sq;
-            if constexpr (AHEAD && K > 0) {
-                pin = a_pin; pj = a_pj; pk = a_pk; wmix = a_wmix; sq = a_sq;     // predicted during the previous bit
-            } else {
-                const Pred P = chain_of(cur_v, cur_b, X.slot);
-                pin = P.pin; pj = P.pj; pk = P.pk; wmix = P.wmix;
-                sq = s_squash[P.p + 2048];
-            }
+            const Pred P = chain_of(cur_v, cur_b, X.slot);
+            const i32 pin = P.pin, pj = P.pj, pk = P.pk, wmix = P.wmix;
+            const i32 sq = s_squash[P.p + 2048];
             // ---- this copy's outcome
             const i32 yh = hyp;
             u32 sN = 0, rNv = 0;
@@ -1278,13 +1153,6 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
                 const bool same = sN == s;
                 nxt_v = same ? nv : rNv;
                 nxt_bs = ((u32)(same ? nb : rNb) & 255u) | (sN << 8);
-            }
-            // ---- the next bit's chain under this copy's outcome (see AHEAD)
-            Pred Q = {0, 0, 0, 0, 0};
-            i32 sq2 = 0;
-            if constexpr (AHEAD && K < 3) {
-                Q = chain_of(nxt_v, (i32)(int8_t)(nxt_bs & 255u), X.slot * 2u + (u32)yh);
-                sq2 = s_squash[Q.p + 2048];
             }
             // ---- the bit (both copies decode it: same code, same window, same bounds).  The split runs on EVERY lane -- lanes that
             // are not a coder hold a range of their own that means nothing and is never renormalised (no memory access outside the
@@ -1336,18 +1204,8 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
                 cur_b = (i32)(int8_t)(bs & 255u);
                 cur_s = bs >> 8;
                 cur_pst = icm_st(cur_v, cur_b);
-                if constexpr (AHEAD) {
-                    const i32 xq = (i32)xchg((u32)sq2), xi = (i32)xchg((u32)Q.pin);
-                    a_sq = mine ? sq2 : xq;
-                    a_pin = mine ? Q.pin : xi;
-                    if constexpr (MIXT) {
-                        const i32 xj = (i32)xchg((u32)Q.pj), xk = (i32)xchg((u32)Q.pk), xw = (i32)xchg((u32)Q.wmix);
-                        a_pj = mine ? Q.pj : xj; a_pk = mine ? Q.pk : xk; a_wmix = mine ? Q.wmix : xw;
-                    }
-                }
             } else {
-                if (HYP4 && bit == 4) sel_alt = y != 0;         // (the copy whose third bit was right holds both outcomes of this one)
-                else row_mine = mine;
+                row_mine = mine;
                 if (bit == 0) {
                     const u32 xh = xchg(hn_spec);
                     hnext_dec = mine ? hn_spec : xh;
@@ -1365,15 +1223,7 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             else { X.r3 = (X.slot & 4u) ? ins : X.r3; X.r2 = (X.slot & 4u) ? X.r2 : ins; }
             X.c8 = (X.c8 << 1) | (u32)y;
             X.slot = (K == 3) ? 1u : (X.slot * 2u + (u32)y);
-            if (HYP4 && bit == 6) {
-                // two bits of the byte's first nibble are known: the second nibble's rows for this copy's outcome of the
-                // third bit, both outcomes of the fourth (see HYP4 above)
-                const u32 c8n = (X.c8 << 2) | ((u32)hyp << 1);
-                prefetch_alt(hctx, c8n | 1u);
-                prefetch_rows(hctx, c8n);
-            }
-            if (HYP4 && bit == 5) row_mine = mine;
-            if (K == 2 && !(HYP4 && bit == 5)) {
+            if (K == 2) {
                 // Three bits of the nibble are known: this copy asks for the rows of the next nibble under ITS outcome of
                 // the fourth.  The request has the whole last bit step (~1000 cycles) to travel before it is needed;
                 // the HBM round trip measured here is ~1350 cycles.
@@ -1463,7 +1313,7 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
 
             X.c8 = 1; X.slot = 1;
             u32 hnext = 0;
-            take_prefetched(bi != 0, std::false_type{});      // rows of this byte's first nibble
+            take_prefetched(bi != 0);      // rows of this byte's first nibble
             if (DEC && pend_store) { dst[pend_pos] = (u8)pend_val; pend_store = false; }   // (see pend_store)
             if (!DEC && is_last) oq_flush();
             if (DEC && mixreg) { if (MIXS) mixs_arrive(); else mixw_arrive(); }
@@ -1477,7 +1327,7 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             step(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
             step(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{});
             step(std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{});     // decode: requests the next rows inside
-            take_prefetched(true, std::true_type{});
+            take_prefetched(true);
             if (DEC && mixreg) { if (MIXS) mixs_arrive(); else mixw_arrive(); }
             if (!DEC) prefetch_rows(hnext, 1u);               // first nibble of the next byte
             nibble_begin();
@@ -1575,18 +1425,9 @@ static bool build_cfg(const DModel *M, Cfg *cfg)
     cfg->n = M->n;
     {
         const char *ev = getenv("ZPQ_CHAIN_G");          // tuning knob
-        const int want = ev ? atoi(ev) : ZPQ_CHAIN_G_DEFAULT;
+        const int want = ev ? atoi(ev) : CHAIN_G_DEFAULT;
         cfg->g = (want == 8 && M->n <= 8) ? 8 : 16;
     }
-    cfg->dbg_ht_and = 0xFFFFFFFFu;
-#ifdef ZPQ_DEBUG_KNOBS
-    {
-        // timing experiments only (make EXTRA=-DZPQ_DEBUG_KNOBS): an AND-mask on hash-table offsets keeps the tables
-        // cache-resident -- the output is WRONG, which is why a normal build cannot reach this
-        const char *ev = getenv("ZPQ_DEBUG_HT_AND");
-        if (ev) cfg->dbg_ht_and = (uint32_t)strtoul(ev, nullptr, 0);
-    }
-#endif
     // Per-block LDS layout.  Tables are indexed by the bit-history state, and lanes of
     // different blocks / components very often hold EQUAL states, so tables whose bases share
     // a bank (all of them, if laid out at 1 KiB multiples) collide on every access -- rocprof
@@ -1645,7 +1486,7 @@ static bool build_cfg(const DModel *M, Cfg *cfg)
     if (cfg->nch_spec && (!mix_ok || cfg->vm_kind != (cfg->nch_spec == 2 ? zpqc::VM_LEVEL1 : zpqc::VM_HASHCHAIN))) {
         cfg->nch_spec = 0;
         const char *ev = getenv("ZPQ_CHAIN_G");
-        const int want = ev ? atoi(ev) : ZPQ_CHAIN_G_DEFAULT;
+        const int want = ev ? atoi(ev) : CHAIN_G_DEFAULT;
         cfg->g = (want == 8 && M->n <= 8) ? 8 : 16;
     }
     const int bpwave2 = 64 / cfg->g;   // blocks one wave carries
@@ -1711,19 +1552,6 @@ extern "C" int zpq_chain_max_wgs(const DModel *M, int cus)
     return cus;   // one workgroup per CU (LDS-bound)
 }
 
-// The two-hypothesis decoder (dense short chains, levels 1-2) reads hash rows through "touched" bitmaps when the slot
-// layout carries them (zpq_touch_layout); the wave-split decoder (opt-in) does not.
-extern "C" int zpq_chain_touch_decode(const DModel *M)
-{
-    Cfg cfg;
-    const char *ev = getenv("ZPQ_DEC_PIPE");
-    if (ev && atoi(ev) != 0) return 0;
-#ifndef ZPQ_TOUCH_DEC
-    return 0;                                                // (measured slower: see `touch` in k_chain)
-#endif
-    return build_cfg(M, &cfg) && !cfg.sparse && !cfg.has_mix2 && (cfg.nch_spec == 2 || cfg.nch_spec == 3) && cfg.g == 8 ? 1 : 0;
-}
-
 // striped host transfers (HIO kernels) exist for the dense short chains: levels 1 and 2
 extern "C" int zpq_chain_has_hio(const DModel *M)
 {
@@ -1777,13 +1605,13 @@ extern "C" int zpq_launch_chain(const DBatch *B, const DModel *hostM, int decode
     // encode uses the pipelined bit step, decode the plain one (measured, see above)
 #define ZPQ_LAUNCH(D, N, MX, GGv, SPv)                                                                   \
     do {                                                                                                 \
-        constexpr bool S_ = (D) ? (ZPQ_CHAIN_SPEC_DEC != 0) : (ZPQ_CHAIN_SPEC_ENC != 0);                 \
+        constexpr bool S_ = (D) ? CHAIN_SPEC_DEC : CHAIN_SPEC_ENC;                                       \
         (void)hipFuncSetAttribute((const void *)zpqc::k_chain<D, S_, N, MX, GGv, SPv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
         hipLaunchKernelGGL((zpqc::k_chain<D, S_, N, MX, GGv, SPv>), dim3(nwg), dim3(threads), lds, stream, *B, cfg); \
     } while (0)
 #define ZPQ_LAUNCH_HIO(D, N)                                                                             \
     do {                                                                                                 \
-        constexpr bool S_ = (D) ? (ZPQ_CHAIN_SPEC_DEC != 0) : (ZPQ_CHAIN_SPEC_ENC != 0);                 \
+        constexpr bool S_ = (D) ? CHAIN_SPEC_DEC : CHAIN_SPEC_ENC;                                       \
         (void)hipFuncSetAttribute((const void *)zpqc::k_chain<D, S_, N, false, 8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
         hipLaunchKernelGGL((zpqc::k_chain<D, S_, N, false, 8, false, true>), dim3(nwg), dim3(threads), lds, stream, *B, cfg); \
     } while (0)

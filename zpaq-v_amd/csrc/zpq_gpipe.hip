@@ -784,27 +784,11 @@ __global__ void __launch_bounds__(1024) k_gpipe(const DBatch B, const GCfg cfg)
 // component's prediction, decodes the bit and hands it back; every wave trains its component and moves to the next bit's
 // contexts.  Against zpq_lanes.hip (lane = component, four blocks per wave) a wave issues only its own type's code, for
 // 64 blocks, and the bit costs one trip to the tables plus the chain of levels.
-#ifndef ZPG_HASH_SPEC
-#define ZPG_HASH_SPEC 0                              // ICM / ISSE asking for the two states the next bit can meet: two random lines of the
-                                                     // state table where one is needed -- measured 2081 ms against 2038 without (same box); 1: timing builds
-#endif
 // Which component types ask for the next bit's entries under both values of the bit -- decided by A/B on one box (C4b, 16 384
 // blocks, decode ms; default 2079-2083): the kernel runs at ~0.85 of the chip's random-line rate, so a request pays only where it
 // brings no new line (CM, MIX2: the neighbour word: 2090 / 2094 without) or takes a whole trip off the end of the prediction
-// chain (SSE, the last level: 2330 without); the MIX's two rows (2001 WITHOUT) and the two states of an ICM / ISSE (2038
-// without) cost more in lines than they hide.
-#ifndef ZPG_CM_SPEC
-#define ZPG_CM_SPEC 1
-#endif
-#ifndef ZPG_MIX2_SPEC
-#define ZPG_MIX2_SPEC 1
-#endif
-#ifndef ZPG_MIX_SPEC
-#define ZPG_MIX_SPEC 0
-#endif
-#ifndef ZPG_SSE_SPEC
-#define ZPG_SSE_SPEC 1                               // an SSE asks for the next bit's two candidate rows (timing builds: 0)
-#endif
+// chain (SSE, the last level: 2330 without); the MIX's two rows (2001 WITHOUT) and the two states of an ICM / ISSE (2081 against
+// 2038 without: two random lines of the state table where one is needed) cost more in lines than they hide.
 constexpr int D_P = L_DT2K + 512;                // i32 p[16][BPW]: this bit's predictions
 constexpr int D_Y = D_P + 16 * BPW * 4;          // u32 y[BPW]
 constexpr int D_ALIVE = D_Y + BPW * 4;           // u32 alive[BPW]: the block has not met its EOF flag yet
@@ -881,23 +865,22 @@ __device__ __forceinline__ void comp_dec(const DStage &S)
     u32 r0 = 0, r1 = 0, r2 = 0, r3 = 0, roff = 0;
     (void)ma; (void)mb; (void)mc; (void)mlimit; (void)mpred; (void)mcand; (void)r0; (void)r1; (void)r2; (void)r3; (void)roff;
     // Inside a nibble the NEXT bit's contexts are known now but for this bit: its table entries are asked for under both values
-    // (CM, MIX2, MIX: neighbouring entries / rows; ICM, ISSE: the two states the nibble's row holds for them) while this bit
+    // (CM, MIX2: neighbouring entries; SSE: the two candidate rows; the others ask when the bit is known, see above) while this bit
     // is still being predicted, and picked when the bit is known.  An entry that this bit's training then rewrites is taken from
     // the training (tr_*), not from the load that went out before it.
-    constexpr bool SPEC = (TYPE == ZT_CM && ZPG_CM_SPEC) || ((TYPE == ZT_ICM || TYPE == ZT_ISSE) && ZPG_HASH_SPEC) || (TYPE == ZT_MIX2 && ZPG_MIX2_SPEC) ||
-                          (TYPE == ZT_MIX && ZPG_MIX_SPEC) || (TYPE == ZT_SSE && ZPG_SSE_SPEC);
+    constexpr bool SPEC = TYPE == ZT_CM || TYPE == ZT_MIX2 || TYPE == ZT_SSE;
     // the entry arrives in nx0 / nx1 / nxw whether asked for early or not, and is taken from there -- or from the last training
     constexpr bool FWD = TYPE == ZT_CM || TYPE == ZT_ICM || TYPE == ZT_ISSE || TYPE == ZT_MIX2 || TYPE == ZT_MIX;   // (an SSE trains its CURRENT row; the next bit's row is patched in LDS if ever hit)
     bool spec = false;
-    u32 sa0 = 0, sa1 = 0, sb0 = 0, sb1 = 0, tr_a = 0xFFFFFFFFu, tr0 = 0, tr1 = 0, yprev = 0;
+    u32 sa0 = 0, sb0 = 0, tr_a = 0xFFFFFFFFu, tr0 = 0, tr1 = 0, yprev = 0;
     u32 nx0 = 0, nx1 = 0;                                        // ... picked as soon as the bit is known, BEFORE this bit's stores go out:
-    i32 swa[8], swb[8], trw[8], nxw[8];                          // a wait placed behind the stores would wait for their acknowledgement too
+    i32 trw[8], nxw[8];                                          // a wait placed behind the stores would wait for their acknowledgement too
     (void)nx0; (void)nx1; (void)nxw;
     u32x4 ra[8], rb[8];                                          // SSE: the next bit's two candidate rows
     bool sok0 = false, sok1 = false, nrow_ok = false;
     u32 nrow = 0;
     (void)ra; (void)rb; (void)sok0; (void)sok1; (void)nrow_ok; (void)nrow;
-    (void)spec; (void)sa0; (void)sa1; (void)sb0; (void)sb1; (void)tr_a; (void)tr0; (void)tr1; (void)yprev; (void)swa; (void)swb; (void)trw;
+    (void)spec; (void)sa0; (void)sb0; (void)tr_a; (void)tr0; (void)tr1; (void)yprev; (void)trw;
 
     for (;;) {
         lds_barrier();                                           // the decoder wave has looked at the EOF flag
@@ -942,10 +925,8 @@ __device__ __forceinline__ void comp_dec(const DStage &S)
                     const u32 dsel = (slotn & 8u) ? ((slotn & 4u) ? r3 : r2) : ((slotn & 4u) ? r1 : r0);
                     st = (dsel >> ((slotn & 3u) * 8u)) & 255u;
                     idx = st;
-                    if (!spec) {
-                        if (TYPE == ZT_ICM) nx0 = cm[st];
-                        else { const uint2 w = *reinterpret_cast<const uint2 *>(cm + st * 2); nx0 = w.x; nx1 = w.y; }
-                    }
+                    if (TYPE == ZT_ICM) nx0 = cm[st];
+                    else { const uint2 w = *reinterpret_cast<const uint2 *>(cm + st * 2); nx0 = w.x; nx1 = w.y; }
                 } else if (TYPE == ZT_MATCH) {
                     if (kb == 0) {                               // the predicted byte, and the candidate position the byte's END will want
                         mpred = ht[wsub(mlimit, mb) & (i32)(ht_len - 1)];
@@ -956,7 +937,7 @@ __device__ __forceinline__ void comp_dec(const DStage &S)
                     if (!spec) nx0 = a16[idx];
                 } else if (TYPE == ZT_MIX) {
                     idx = (u32)(wadd((i32)hctx, (i32)c8 & cmask) & (cc - 1));
-                    if (!spec) load_row(cm + (size_t)wmul((i32)idx, climit), nxw);
+                    load_row(cm + (size_t)wmul((i32)idx, climit), nxw);
                 } else if (TYPE == ZT_SSE) {
                     idx = (hctx + c8) * 32u;                     // the row of this bit context; entry = row + f(input)
                     if (spec) row_ok = nrow_ok;                  // (the row was put into LDS when the last bit became known)
@@ -970,8 +951,8 @@ __device__ __forceinline__ void comp_dec(const DStage &S)
                 }
             }
             // ---- the next bit's entries under both values of this bit
-            // (a bit-history row changes with the nibble; everything else only needs the byte to go on: hctx stays)
-            const bool spec_next = SPEC && alive && kb != 7 && !((TYPE == ZT_ICM || TYPE == ZT_ISSE) && kb == 3);
+            // (they only need the byte to go on: hctx stays)
+            const bool spec_next = SPEC && alive && kb != 7;
             if (spec_next) {
                 const u32 hm0 = kb == 3 ? (((hmap4 & 0xfu) << 5) | 1u) : ((hmap4 & 0x1f0u) | (((hmap4 & 0xfu) * 2u) & 0xfu));
                 const u32 hm1 = kb == 3 ? (((hmap4 & 0xfu) << 5) | 17u) : ((hmap4 & 0x1f0u) | (((hmap4 & 0xfu) * 2u + 1u) & 0xfu));
@@ -980,22 +961,9 @@ __device__ __forceinline__ void comp_dec(const DStage &S)
                 if (TYPE == ZT_CM) {
                     sa0 = cm[(hctx ^ hm0) & (cm_len - 1u)];
                     sb0 = cm[(hctx ^ hm1) & (cm_len - 1u)];
-                } else if (TYPE == ZT_ICM || TYPE == ZT_ISSE) {
-                    // (a 64-bit shift, not a four-way select: two of those in a row the compiler turns into a stack array)
-                    const u64 rlo = (u64)r0 | ((u64)r1 << 32), rhi = (u64)r2 | ((u64)r3 << 32);
-                    auto state_at = [&](const u32 slotn) -> u32 { return (u32)(((slotn & 8u) ? rhi : rlo) >> ((slotn & 7u) * 8u)) & 255u; };
-                    const u32 st0 = state_at(hm0 & 15u), st1 = state_at(hm1 & 15u);
-                    if (TYPE == ZT_ICM) { sa0 = cm[st0]; sb0 = cm[st1]; }
-                    else {
-                        const uint2 wa = *reinterpret_cast<const uint2 *>(cm + st0 * 2), wb = *reinterpret_cast<const uint2 *>(cm + st1 * 2);
-                        sa0 = wa.x; sa1 = wa.y; sb0 = wb.x; sb1 = wb.y;
-                    }
                 } else if (TYPE == ZT_MIX2) {
                     sa0 = a16[(hctx + (c80 & (u32)cmask)) & (u32)(cc - 1)];
                     sb0 = a16[(hctx + (c81 & (u32)cmask)) & (u32)(cc - 1)];
-                } else if (TYPE == ZT_MIX) {
-                    load_row(cm + (size_t)wmul(wadd((i32)hctx, (i32)c80 & cmask) & (cc - 1), climit), swa);
-                    load_row(cm + (size_t)wmul(wadd((i32)hctx, (i32)c81 & cmask) & (cc - 1), climit), swb);
                 } else if (TYPE == ZT_SSE) {
                     const u32 i0 = (hctx + c80) * 32u, i1 = (hctx + c81) * 32u;
                     sok0 = (i32)i0 >= 0 && i0 + 32u <= cm_len;
@@ -1070,11 +1038,7 @@ __device__ __forceinline__ void comp_dec(const DStage &S)
             const u64 t3 = __builtin_readcyclecounter();
 #endif
             if (spec_next) {
-                nx0 = y ? sb0 : sa0; nx1 = y ? sb1 : sa1;
-                if (TYPE == ZT_MIX) {
-#pragma unroll
-                    for (int l = 0; l < 8; l++) nxw[l] = y ? swb[l] : swa[l];
-                }
+                nx0 = y ? sb0 : sa0;
                 if (TYPE == ZT_SSE) {                            // (this bit's entries are in v0 / v1 already: the LDS row is free)
                     nrow_ok = y ? sok1 : sok0;
                     nrow = (hctx + ((c8 << 1) | (u32)y)) * 32u;

@@ -126,7 +126,6 @@ struct InWin {
 struct Req {
     u32x4 A, B, C, tags;
     u32 po, chk, key, si, off;
-    u32 tw;              // dense table that is not cleared (zpq_touch_layout): the word holding the line's four "touched" bits
 };
 // a nibble's bit-history row (byte 0 = check) and its tbase offset
 struct Row {
@@ -147,18 +146,8 @@ __device__ __forceinline__ void comp_loop(const StageArgs &S)
     const u16 *s_squash = reinterpret_cast<const u16 *>(lds + LDS_SQUASH);
     const u8 *s_ns = lds + LDS_NS;
     auto stretch_of = [&](u32 cm) -> i32 {                              // see zpq_chain.hip
-#ifdef ZPQ_STRETCH_ENDS
-        u32 q = cm >> 8;
-        q = min(max(q, 1u), 32767u);
-        const u32 wv = s_stretch[q >> 4];
-        const u32 ei = q < 64u ? q : (q - 32704u + 64u);
-        const i32 endv = (i32)(int16_t)s_stretch[2048 + (ei & 127u)];
-        const i32 midv = (i32)(int16_t)(wv >> 16) + __popc(wv & ((2u << (q & 15u)) - 1u) & 0xFFFEu);
-        return (q < 64u || q >= 32704u) ? endv : midv;
-#else
         const u32 wv = s_stretch[(cm >> 12) & 2047u];                   // (an ICM counter's index stays below 32767)
         return ((i32)wv >> 16) + (i32)__popc(__builtin_amdgcn_ubfe(wv, 1u, (cm >> 8) & 15u));
-#endif
     };
     const int ci = S.ci;
     const DComp &C = M.comp[ci];
@@ -168,19 +157,8 @@ __device__ __forceinline__ void comp_loop(const StageArgs &S)
     u8 *const slot = S.slot;
     u32 *const sp_tags = reinterpret_cast<u32 *>(slot + C.sp_tag_off);
     u8 *const tbase = sp_cap ? slot + C.sp_line_off : slot + C.ht_off;
-    // A dense table may come WITHOUT having been cleared (zpq_touch_layout: 12 MiB per level-2 block otherwise): one
-    // "touched" bit per 16-byte row says whether the row has been written in this block; an untouched row reads as zeros.
-    // Built, parity-green and MEASURED: level 2 encode 135-145 ms against 123-126 ms with the 15 ms of clearing (level 1 133
-    // against 136, level 3 dense 167 against 167.5) -- the extra load per request, the twelve selects and the word store cost
-    // what the clearing costs.  Compiled only with -DZPP_TOUCH (tools/variant.sh).
-#ifdef ZPP_TOUCH
-    constexpr bool TOUCHC = !SP;
-#else
-    constexpr bool TOUCHC = false;
-#endif
-    const bool touch = TOUCHC && C.tb_off != 0;
-    u32 *const tb32 = reinterpret_cast<u32 *>(slot + (touch ? C.tb_off : 0));
-    u32 tc_word = 0xFFFFFFFFu, tc_bit = 0;             // the last bit set: a request that was in flight then holds a stale word
+    // (A "touched" bitmap in place of clearing the dense tables: parity-green, level 2 encode 135-145 ms against 123-126 with
+    //  the clearing -- EXPERIMENTS.md 4.1 "Zero-fill replaced by a touched bitmap".)
     const int sizebits = C.a + 2;
     u32 *const t32 = reinterpret_cast<u32 *>(S.my + cfg.lds_off32[ci]);
     u8 *const t8 = S.my + cfg.lds_off8[ci];
@@ -228,8 +206,6 @@ __device__ __forceinline__ void comp_loop(const StageArgs &S)
         const u32 h0 = (cx * 16u) & ht_mask;
         u32 pox = h0;
         q.key = 0; q.si = 0; q.off = 0; q.tags = u32x4{0, 0, 0, 0};
-        q.tw = 0xFFFFFFFFu;
-        if (TOUCHC) q.tw = tb32[touch ? (h0 >> 9) : 0u];
         if (SP && sp_cap) {
             q.key = (h0 >> 6) + 1u;
             q.si = __umulhi(q.key * 0x9E3779B1u, sp_cap);
@@ -282,16 +258,6 @@ __device__ __forceinline__ void comp_loop(const StageArgs &S)
                 ZPP_LOAD_ROWS(q, q.po);
             }
         }
-        u32 tw = 0xFFFFFFFFu;
-        if (TOUCHC) {
-            // (the bit of the nibble that was resolved while this request was in flight is not in its word yet)
-            tw = touch ? (q.tw | ((q.po >> 9) == tc_word ? tc_bit : 0u)) : 0xFFFFFFFFu;
-            const u32 rb = (q.po >> 4) & 31u;
-            const bool ta = ((tw >> rb) & 1u) != 0, tb = ((tw >> (rb ^ 1u)) & 1u) != 0, tc = ((tw >> (rb ^ 2u)) & 1u) != 0;
-            q.A = u32x4{ta ? q.A.x : 0u, ta ? q.A.y : 0u, ta ? q.A.z : 0u, ta ? q.A.w : 0u};
-            q.B = u32x4{tb ? q.B.x : 0u, tb ? q.B.y : 0u, tb ? q.B.z : 0u, tb ? q.B.w : 0u};
-            q.C = u32x4{tc ? q.C.x : 0u, tc ? q.C.y : 0u, tc ? q.C.z : 0u, tc ? q.C.w : 0u};
-        }
         const u32 pa = q.po, pb = q.po ^ 16u, pc = q.po ^ 32u;
         const bool a1 = have1 && pa == L1.off, b1 = have1 && pb == L1.off, c1 = have1 && pc == L1.off;
         const bool a2 = FWD2 && have2 && pa == L2.off, b2 = FWD2 && have2 && pb == L2.off, c2 = FWD2 && have2 && pc == L2.off;
@@ -327,13 +293,6 @@ __device__ __forceinline__ void comp_loop(const StageArgs &S)
         }
 #ifndef ZPP_DEBUG_NO_ROWS
         if (have1) *reinterpret_cast<u32x4 *>(tbase + poff2) = u32x4{L1.x, L1.y, L1.z, L1.w};
-        if (TOUCHC) {
-            // the resolved row counts as written from now on (it is stored when the next nibble's rows are consumed; until
-            // then every request that meets it takes it from the registers)
-            const u32 nbit = 1u << ((R.off >> 4) & 31u);
-            if (touch && (tw & nbit) == 0u) tb32[R.off >> 9] = tw | nbit;
-            tc_word = R.off >> 9; tc_bit = nbit;
-        }
 #endif
         return R;
     };
@@ -562,7 +521,7 @@ __device__ __forceinline__ void hist_loop(const StageArgs &S, const int delay)
         const u32 cx = hc + 16u * c8v;
         q.chk = (cx >> sizebits) & 255u;
         q.po = (cx * 16u) & ht_mask;
-        q.key = 0; q.si = 0; q.off = 0; q.tags = u32x4{0, 0, 0, 0}; q.tw = 0;
+        q.key = 0; q.si = 0; q.off = 0; q.tags = u32x4{0, 0, 0, 0};
         ZPH_LOAD_ROWS(q, q.po);
         return q;
     };
@@ -658,7 +617,7 @@ __device__ __forceinline__ void hist_loop(const StageArgs &S, const int delay)
     Req reqX, reqY;
     {
         const u32x4 z4 = {0, 0, 0, 0};
-        reqX.A = z4; reqX.B = z4; reqX.C = z4; reqX.tags = z4; reqX.po = 0; reqX.chk = 0; reqX.key = 0; reqX.si = 0; reqX.off = 0; reqX.tw = 0;
+        reqX.A = z4; reqX.B = z4; reqX.C = z4; reqX.tags = z4; reqX.po = 0; reqX.chk = 0; reqX.key = 0; reqX.si = 0; reqX.off = 0;
         reqY = reqX;
     }
     if (S.active && total) {
@@ -715,18 +674,8 @@ __device__ __forceinline__ void pred_loop(const StageArgs &S, const int delay)
     const u16 *s_squash = reinterpret_cast<const u16 *>(lds + LDS_SQUASH);
     const u32 *s_stretch = reinterpret_cast<const u32 *>(lds + LDS_STRETCH);
     auto stretch_of = [&](u32 cm) -> i32 {                              // see zpq_chain.hip
-#ifdef ZPQ_STRETCH_ENDS
-        u32 q = cm >> 8;
-        q = min(max(q, 1u), 32767u);
-        const u32 wv = s_stretch[q >> 4];
-        const u32 ei = q < 64u ? q : (q - 32704u + 64u);
-        const i32 endv = (i32)(int16_t)s_stretch[2048 + (ei & 127u)];
-        const i32 midv = (i32)(int16_t)(wv >> 16) + __popc(wv & ((2u << (q & 15u)) - 1u) & 0xFFFEu);
-        return (q < 64u || q >= 32704u) ? endv : midv;
-#else
         const u32 wv = s_stretch[(cm >> 12) & 2047u];                   // (an ICM counter's index stays below 32767)
         return ((i32)wv >> 16) + (i32)__popc(__builtin_amdgcn_ubfe(wv, 1u, (cm >> 8) & 15u));
-#endif
     };
     const int ci = S.ci;
     const bool is_last = PAIR ? ci == NCH - 1 : IS_LAST;
@@ -945,10 +894,6 @@ __device__ __forceinline__ void coder_loop_d(const StageArgs &S, Coder &X, const
                 const u32 hv = pw >> ((kb & 1) * 16);
                 const u32 p16 = (hv & 0x7FFFu) * 2u + 1u;               // encoder.v:60
                 const bool y = (hv & 0x8000u) != 0;
-#ifdef ZPP_DEBUG_DUMP   // debug aid: the link values instead of the coded stream
-                X.put(hv & 255u); X.put((hv >> 8) & 255u);
-                continue;
-#endif
                 const u32 mid = X.low + mul_shr16(X.high - X.low, p16);
                 X.high = y ? mid : X.high;
                 X.low = y ? X.low : mid + 1;
@@ -1233,16 +1178,6 @@ static bool pipe_layout(const Cfg &cfg, int bpw, zpqp::PipeLds *L, size_t *lds_b
 // The wave-pipelined encoder exists for the dense and line-store chains of levels 1-5.  ZPQ_ENC_PIPE=0 keeps the
 // lane-per-component encoder (tests compare the two).
 // (a batch of fewer than 12 resident blocks stays with the lane-per-component encoder: see zpq_launch_pipe)
-// 1 = this build's encoder reads dense hash rows through "touched" bitmaps (zpq_touch_layout)
-extern "C" int zpq_pipe_touch(void)
-{
-#ifdef ZPP_TOUCH
-    return 1;
-#else
-    return 0;
-#endif
-}
-
 extern "C" int zpq_pipe_applies(const DModel *M, int blocks_per_wg, int nslots)
 {
     if (nslots < 12) return 0;
