@@ -19,14 +19,16 @@ import oracle_lib as O  # noqa: E402
 import workload as W  # noqa: E402
 from inputs import C4B  # noqa: E402
 import chain_models as CM  # noqa: E402
+import general_models as GM  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--seconds", type=float, default=300)
 ap.add_argument("--seed", type=int, default=1)
 ap.add_argument("--only", type=int, default=-1, help="run only batch number N of the seed's sequence")
-ap.add_argument("--general", action="store_true", help="general models: random mixes of the nine component types (inputs = earlier "
-                "components, hash-chain program), C4b, levels 2-3 as general models -- the wave-per-component encoder k_gpipe in its "
-                "byte-batched and bit-serial forms, decoded back by k_rows")
+ap.add_argument("--general", action="store_true", help="general models (tests/general_models.py: any mix of the nine component types, "
+                "sizes, rates and limits on their edges, forward references, any program), C4b, levels 2-3 as general models -- k_gpipe in "
+                "its byte-batched and bit-serial forms, k_rows / k_lanes, k_generic; decoded back by the default decoder and by "
+                "k_rows / k_lanes; the summary counts the routes")
 ap.add_argument("--chains", action="store_true", help="random chain models (tests/chain_models.py: any chain length, table sizes, "
                 "hh / hm, program and MIX2) -- the specialised and the runtime-loop chain kernels; the summary counts the routes")
 ap.add_argument("--levels", default="", help="comma-separated levels to draw from instead of the default mix (e.g. 3,4: the round-4 decoders)")
@@ -40,44 +42,6 @@ t_end = time.time() + a.seconds
 names = {}
 routes = {}
 nbatch = nblocks = nbytes = 0
-
-
-HC = [74, 18, 104, 95, 0] + [59, 112, 25] * 7 + [59, 112, 56, 0]
-
-
-def random_model(r):
-    """A header with 1..12 components of random type whose inputs are earlier components."""
-    n = r.randint(1, 12)
-    comps = []
-    for i in range(n):
-        kinds = [1, 2, 3, 4] + ([5, 6, 7, 8, 9] * 2 if i else [])
-        t = r.choice(kinds)
-        j = r.randrange(i) if i else 0
-        k = r.randrange(i) if i else 0
-        if t == 1:
-            c = [1, r.randrange(256)]
-        elif t == 2:
-            c = [2, r.randint(6, 16), r.randint(1, 255)]
-        elif t == 3:
-            c = [3, r.randint(5, 14)]
-        elif t == 4:
-            c = [4, r.randint(6, 14), r.randint(1, 14)]
-        elif t == 5:
-            c = [5, j, k, r.randrange(256)]
-        elif t == 6:
-            c = [6, r.randint(0, 10), j, k, r.randint(1, 30), r.choice([0, 255, 15, 3])]
-        elif t == 7:
-            m = r.randint(1, min(8, i))
-            c = [7, r.randint(0, 8), r.randint(0, i - m), m, r.randint(1, 30), r.choice([0, 255, 15])]
-        elif t == 8:
-            c = [8, r.randint(5, 14), j]
-        else:
-            c = [9, r.randint(1, 8), j, r.randint(1, 32), r.randint(1, 255)]
-        comps.append(c)
-    b = [4, 16, 0, 0, n]
-    for c in comps:
-        b += c
-    return bytes(b + [0] + HC), comps
 
 
 def make(kind, n, r):
@@ -111,12 +75,11 @@ while time.time() < t_end:
     lanes_flag = 0
     if a.general:
         which = r.choice(["rnd", "rnd", "rnd", "c4b", "c4b", 2, 3])
-        lanes_flag = z.FLAG_LANES if which in (2, 3) else 0
+        lanes_flag = z.FLAG_LANES if which in (2, 3, "rnd") else 0    # (a chain-shaped draw stays with the general kernels)
     if a.chains:
         which = "chain"
     if which == "rnd":
-        header, comps = random_model(r)
-        which = "rnd%s" % comps
+        header = GM.random_general(r, big=True)
     elif which == "chain":
         header = CM.random_chain(r, big=True)
     else:
@@ -125,6 +88,10 @@ while time.time() < t_end:
     rclass = CM.route_class(CM.route(z, model)) if which == "chain" else None
     if rclass:
         which = "chain %s %s" % (rclass, header.hex())
+    gclass = None
+    if which == "rnd":
+        gclass = GM.route_class(header, GM.route(z, model))
+        which = "rnd %s %s" % (gclass, header.hex())
     nb = r.choice([1, 2, 5, 11, 12, 13, 16, 17, 31, 33, 64, 100, 150])
     if which in (4, 5, "c4b") and not a.general:
         nb = min(nb, 33)
@@ -137,6 +104,8 @@ while time.time() < t_end:
     env = {}
     if a.general:
         nb = r.choice([1, 2, 5, 33, 64, 65, 100, 150, 200])
+        if gclass and any(c[0] in (GM.CM, GM.ICM, GM.ISSE) and c[1] >= 18 for c in GM.components(header)):
+            nb = min(nb, 33)                                 # (the oracle clears every table per block)
         blocks = [make(r.randrange(6), r.randint(0, maxlen) if r.random() < 0.8 else maxlen, r) for _ in range(nb)]
         if r.random() < 0.3:
             env["ZPQ_GPIPE_BATCH"] = "0"
@@ -178,6 +147,14 @@ while time.time() < t_end:
         for i in range(nb):
             if i not in bigd:
                 assert dec[i] == blocks[i] and int(consumed[i]) == len(want[i]), (desc, "decode of block", i)
+        if a.general and dname == "k_gdec<decode>":          # the lane-per-component decoder on the same streams
+            os.environ["ZPQ_DEC_GPIPE"] = "0"
+            try:
+                dec2, dstatus2, consumed2, _, _ = ctx.decode_blocks(model, want, cap=maxlen + 16, flags=flags)
+            finally:
+                del os.environ["ZPQ_DEC_GPIPE"]
+            assert ctx.last_kernel_name in ("k_rows<decode>", "k_lanes<decode>"), (desc, ctx.last_kernel_name)
+            assert dec2 == blocks and (dstatus2 == 0).all() and [int(c) for c in consumed2] == [len(w) for w in want], (desc, "second decoder")
     except AssertionError as e:
         print("MISMATCH", e, flush=True)
         sys.exit(1)
@@ -187,11 +164,11 @@ while time.time() < t_end:
         if budget:
             L.zpq_ctx_set_state_budget(ctx.h, 150 << 30)
     names[(ename, dname)] = names.get((ename, dname), 0) + 1
-    if rclass:
-        routes[rclass] = routes.get(rclass, 0) + 1
+    if rclass or gclass:
+        routes[rclass or gclass] = routes.get(rclass or gclass, 0) + 1
     nblocks += nb
     nbytes += sum(len(b) for b in blocks)
     if nbatch % 20 == 0:
         print("%d batches, %d blocks, %.1f MB ok; last: %s -> %s/%s slots %d" % (nbatch, nblocks, nbytes / 1e6, desc, ename, dname, slots), flush=True)
 print("DONE: %d batches, %d blocks, %.1f MB, all equal to the oracle; kernels used: %s%s" % (
-    nbatch, nblocks, nbytes / 1e6, names, "; chain routes: %s" % dict(sorted(routes.items())) if routes else ""))
+    nbatch, nblocks, nbytes / 1e6, names, "; routes: %s" % dict(sorted(routes.items())) if routes else ""))
