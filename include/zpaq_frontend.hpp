@@ -201,8 +201,12 @@ struct ArchiveFile {
 // independent blocks instead of one serial one.  The first block carries the file's name and comment,
 // the others an empty name -- libzpaq's convention for "more of the previous file".  Still a valid ZPAQ
 // level-1 stream; the reference's extractor would see the extra blocks as files without a name.
+// solid_files = N > 1 (NOT reference behaviour either): N consecutive pieces -- files, or their fragments -- share one
+// block, a segment each with its own name, comment and SHA-1, so that the model carries over from file to file
+// (compressor.v:238-245): the layout the reference's extractor reads (cmd/main.v:349-380) and its writer never makes.
+// The blocks are coded as block sets (zpq_blockset_*), one launch per round of segments.  0 or 1 = one block per piece.
 int archive_add(zpq_ctx *ctx, int level, const std::vector<ArchiveFile> &files, std::vector<uint8_t> *archive,
-                size_t fragment_bytes = 0);
+                size_t fragment_bytes = 0, int solid_files = 0);
 // run_extract / run_list (cmd/main.v:342-380,440-465): every segment of every block, in archive
 // order.  Single-segment modelled blocks are decoded together in one batch; anything else
 // (store mode, several segments per block) goes through Decompresser.  want_data = false keeps
@@ -210,10 +214,11 @@ int archive_add(zpq_ctx *ctx, int level, const std::vector<ArchiveFile> &files, 
 // Several GPUs: block b -> ctxs[b mod G], one host thread per context, no collective; results are in
 // archive order and identical for any G (ctxs[0] also serves the sequential replay path).
 int archive_add(const std::vector<zpq_ctx *> &ctxs, int level, const std::vector<ArchiveFile> &files, std::vector<uint8_t> *archive,
-                size_t fragment_bytes = 0);
+                size_t fragment_bytes = 0, int solid_files = 0);
 // archive_add over caller-owned bytes: no copy of the file contents on the way to the GPU (what the flat C surface uses)
 int archive_add_views(const std::vector<zpq_ctx *> &ctxs, int level, int nfiles, const char *const *names, const char *const *comments,
-                      const uint8_t *const *data, const uint64_t *lens, std::vector<uint8_t> *archive, size_t fragment_bytes = 0);
+                      const uint8_t *const *data, const uint64_t *lens, std::vector<uint8_t> *archive, size_t fragment_bytes = 0,
+                      int solid_files = 0);
 // join_unnamed: a segment without a name is appended to the file before it (archives written with fragment_bytes).
 int archive_extract(zpq_ctx *ctx, const uint8_t *arc, size_t n, bool want_data, std::vector<ArchiveFile> *files,
                     bool join_unnamed = false);
@@ -261,6 +266,10 @@ zpqf_archive *zpqf_archive_add(zpq_ctx *ctx, int level, int nfiles, const char *
 zpqf_archive *zpqf_archive_add_multi(zpq_ctx *const *ctxs, int nctx, int level, int nfiles, const char *const *names,
                                      const char *const *comments, const uint8_t *const *data, const uint64_t *lens,
                                      uint64_t fragment_bytes, int *rc);
+/* the same with solid_files pieces per block (archive_add's solid_files; ctxs may hold NULL at level 0) */
+zpqf_archive *zpqf_archive_add_solid(zpq_ctx *const *ctxs, int nctx, int level, int nfiles, const char *const *names,
+                                     const char *const *comments, const uint8_t *const *data, const uint64_t *lens,
+                                     uint64_t fragment_bytes, int solid_files, int *rc);
 zpqf_archive *zpqf_archive_extract_multi(zpq_ctx *const *ctxs, int nctx, const uint8_t *arc, size_t n, int want_data, int *rc);
 size_t zpqf_archive_bytes(zpqf_archive *, const uint8_t **p);
 zpqf_archive *zpqf_archive_extract(zpq_ctx *ctx, const uint8_t *arc, size_t n, int want_data /* bit 0: data, bit 1: join unnamed */, int *rc);

@@ -214,6 +214,35 @@ int zpq_block_decode_segment(zpq_block *, const uint8_t *in, size_t n, uint32_t 
                              uint8_t *out, size_t cap, size_t *out_len, size_t *consumed,
                              uint32_t *final_code, uint32_t *first_byte);
 
+/*
+ * A SET of such blocks, coded a segment of each per call: what a front end that puts several segments into every block
+ * needs (the reference's extractor loops find_filename inside each block, cmd/main.v:349-380; a writer may put several
+ * files into one block the same way).  Per member a call is exactly zpq_block_{encode,decode}_segment -- model tables,
+ * z.h, z.m and the VM registers carry over from the member's previous segment, the coder and c8 / hmap4 / h[] start
+ * again (compressor.v:238-245, decompressor.v:413-418, predictor.v:827-833) -- but all listed members go through ONE
+ * launch, their state handed from launch to launch through the set's own state slots.
+ *   zpq_blockset_create   nmembers x "z.clear(); inith(); initp(); pr.init(&z)" (compressor.v:147-185).  max_member_bytes is
+ *                         the promise for a member's bytes over ALL its segments: it sizes the compact line store the way
+ *                         zpq_ctx_set_max_block_bytes does for a block (lines accumulate across segments); 0 = the ctx's
+ *                         setting.  The slots count against the ctx's state budget: ZPQ_E_NOMEM if the set does not fit.
+ *   zpq_blockset_capacity members one set of this model may hold on this ctx (< 0 = ZPQ_E_*).
+ *   zpq_blockset_{encode,decode}_segments   one segment for each of the n listed members.  member[] = n distinct indices in
+ *                         any order (NULL = 0 .. n-1); the other arguments as for zpq_encode_blocks / zpq_decode_blocks,
+ *                         entry i belonging to member[i].  Host pointers, synchronous on the ctx stream.
+ * A member whose segment ends with a status other than ZPQ_OK (ZPQ_E_OVERFLOW, ZPQ_E_TOOBIG, ZPQ_E_VMSTEPS) has FAILED:
+ * later calls report that status for it without coding, the other members are untouched.  ZPQ_FLAG_NOEOF: ZPQ_E_ARG.
+ * Lifetime as for zpq_block: the ctx orphans its sets (calls then return ZPQ_E_CLOSED), a set keeps its model alive.
+ */
+typedef struct zpq_blockset zpq_blockset;
+int zpq_blockset_create(zpq_ctx *, const zpq_model *, int nmembers, uint64_t max_member_bytes, zpq_blockset **out);
+void zpq_blockset_destroy(zpq_blockset *);
+int zpq_blockset_capacity(zpq_ctx *, const zpq_model *, uint64_t max_member_bytes);
+int zpq_blockset_encode_segments(zpq_blockset *, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
+                                 uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status);
+int zpq_blockset_decode_segments(zpq_blockset *, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
+                                 uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, uint32_t *consumed,
+                                 uint32_t *final_code, uint32_t *first_byte, int32_t *status);
+
 /* ---- inspection / test hooks ---- */
 /* squash_table / stretch_table as built at start-up (predictor.v:11-15,21-96). */
 int zpq_tables(int32_t *squash4096, int32_t *stretch32768);

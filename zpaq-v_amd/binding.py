@@ -112,6 +112,11 @@ def lib():
     L.zpq_block_destroy.argtypes = [vp]
     L.zpq_block_encode_segment.argtypes = [vp, u8p, C.c_size_t, u32, vp, C.c_size_t, vp]
     L.zpq_block_decode_segment.argtypes = [vp, u8p, C.c_size_t, u32, vp, C.c_size_t, vp, vp, vp, vp]
+    L.zpq_blockset_create.argtypes = [vp, vp, i32, u64, vp]
+    L.zpq_blockset_destroy.argtypes = [vp]
+    L.zpq_blockset_capacity.argtypes = [vp, vp, u64]
+    L.zpq_blockset_encode_segments.argtypes = [vp, i32, vp, vp, vp, u32, vp, vp, vp, vp]
+    L.zpq_blockset_decode_segments.argtypes = [vp, i32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
     L.zpq_tables.argtypes = [vp, vp]
     L.zpq_tables_ex.argtypes = [vp, vp, vp]
     L.zpq_debug_contexts.argtypes = [vp, vp, u8p, C.c_size_t, vp]
@@ -278,6 +283,13 @@ class Context:
             raise ZpqError(n, "zpq_ctx_resident_capacity")
         return n
 
+    def blockset_capacity(self, model, max_member_bytes=0):
+        """Members one BlockSet of `model` may hold on this GPU (zpq_blockset_capacity)."""
+        n = lib().zpq_blockset_capacity(self.h, model.h, max_member_bytes)
+        if n < 0:
+            raise ZpqError(n, "zpq_blockset_capacity")
+        return n
+
     def encode_blocks(self, model, blocks, flags=FLAG_PP, cap=None):
         nb = len(blocks)
         in_off = _offsets([len(b) for b in blocks])
@@ -389,3 +401,70 @@ class Block:
                                            C.byref(cons), C.byref(code), C.byref(first)),
             "zpq_block_decode_segment")
         return out.raw[:olen.value], cons.value, code.value, first.value
+
+
+class BlockSet:
+    """N ZPAQ blocks whose model state persists across segments, coded a segment of each per call (zpq_blockset):
+    every call is one launch for all listed members.  `members` = distinct member indices in any order (None =
+    0 .. n-1); a member whose segment failed keeps reporting that status."""
+
+    def __init__(self, ctx, model, nmembers, max_member_bytes=0):
+        self.ctx, self.model, self.nmembers = ctx, model, nmembers
+        self.h = C.c_void_p()
+        _ck(lib().zpq_blockset_create(ctx.h, model.h, nmembers, max_member_bytes, C.byref(self.h)), "zpq_blockset_create")
+        ctx._children.add(self)
+
+    def close(self):
+        if getattr(self, "h", None) and _LIB is not None:
+            _LIB.zpq_blockset_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if not _FINALIZING:
+            self.close()
+
+    @staticmethod
+    def _members(members, n):
+        if members is None:
+            return None, None
+        arr = np.asarray(members, dtype=np.int32)
+        assert len(arr) == n
+        return arr, arr.ctypes.data
+
+    def encode_segments(self, segments, members=None, flags=FLAG_PP, cap=None):
+        n = len(segments)
+        keep, mp = self._members(members, n)
+        in_off = _offsets([len(b) for b in segments])
+        src = np.frombuffer(b"".join(segments) + b"\0", dtype=np.uint8)
+        if isinstance(cap, (list, tuple)):                 # one output capacity per segment
+            caps = [int(x) for x in cap]
+        else:
+            caps = [cap if cap is not None else len(b) * 17 + 4096 for b in segments]
+        out_off = _offsets(caps)
+        out = np.zeros(int(out_off[-1]) + 1, dtype=np.uint8)
+        out_len = np.zeros(n, dtype=np.uint32)
+        status = np.zeros(n, dtype=np.int32)
+        _ck(lib().zpq_blockset_encode_segments(self.h, n, mp, src.ctypes.data, in_off.ctypes.data, flags, out.ctypes.data,
+                                               out_off.ctypes.data, out_len.ctypes.data, status.ctypes.data),
+            "zpq_blockset_encode_segments")
+        res = [out[int(out_off[i]):int(out_off[i]) + min(int(out_len[i]), caps[i])].tobytes() for i in range(n)]
+        return res, status, out_len
+
+    def decode_segments(self, coded, cap, members=None, flags=FLAG_PP):
+        n = len(coded)
+        keep, mp = self._members(members, n)
+        in_off = _offsets([len(b) for b in coded])
+        src = np.frombuffer(b"".join(coded) + b"\0", dtype=np.uint8)
+        out_off = _offsets([cap] * n)
+        out = np.zeros(int(out_off[-1]) + 1, dtype=np.uint8)
+        out_len = np.zeros(n, dtype=np.uint32)
+        consumed = np.zeros(n, dtype=np.uint32)
+        code = np.zeros(n, dtype=np.uint32)
+        first = np.zeros(n, dtype=np.uint32)
+        status = np.zeros(n, dtype=np.int32)
+        _ck(lib().zpq_blockset_decode_segments(self.h, n, mp, src.ctypes.data, in_off.ctypes.data, flags, out.ctypes.data,
+                                               out_off.ctypes.data, out_len.ctypes.data, consumed.ctypes.data,
+                                               code.ctypes.data, first.ctypes.data, status.ctypes.data),
+            "zpq_blockset_decode_segments")
+        res = [out[int(out_off[i]):int(out_off[i]) + min(int(out_len[i]), cap)].tobytes() for i in range(n)]
+        return res, status, consumed, code, first

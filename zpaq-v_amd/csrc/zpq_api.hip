@@ -138,6 +138,9 @@ struct zpq_ctx {
     uint32_t *h_gate = nullptr;            // pinned, device-visible: "the rest of the striped upload has arrived"
     std::mutex mu;
     std::vector<zpq_block *> children;     // blocks created on this ctx and not yet destroyed (guarded by g_reg_mu)
+    std::vector<zpq_blockset *> sets;      // block sets likewise
+    uint64_t set_bytes = 0;                // state slots held by block sets: they count against `budget`
+    uint64_t pool_budget() const { return budget > set_bytes ? budget - set_bytes : 0; }   // what is left for the slot pool
 };
 
 // ------------------------------------------------------------------ handle lifetime
@@ -181,6 +184,22 @@ struct zpq_block {
     bool lazy = false;
     std::vector<uint8_t> lazy_in;
     uint32_t lazy_flags = 0;
+};
+
+// N blocks whose model state persists across segments, coded a segment of each per launch (zpq_blockset_*).  The state
+// lives in the set's own slots, in the layout chosen when the set is made: chain models on k_chain<..., KEEP> (dense tables
+// or the line store, sized by max_member_bytes), every other model on k_generic with ZB_KEEP_STATE, a launch per member.
+struct zpq_blockset {
+    zpq_ctx *ctx = nullptr;        // nullptr once the ctx has been destroyed (orphaned set)
+    const zpq_model *model = nullptr;   // the set holds a reference
+    int nmembers = 0;
+    bool chain = false;
+    uint32_t sp = 0;               // line-store capacity (lines), 0 = dense tables
+    DModel layout;                 // what the kernels see
+    uint8_t *slots = nullptr;
+    uint64_t bytes = 0;
+    std::vector<int32_t> failed;   // per member: ZPQ_OK, or the status its first failing segment ended with (sticky)
+    std::vector<uint8_t> fresh;    // per member: no segment coded yet (the generic route initialises in-kernel)
 };
 
 // ------------------------------------------------------------------ ctx
@@ -270,6 +289,13 @@ extern "C" void zpq_ctx_destroy(zpq_ctx *c) try
             b->ctx = nullptr;
         }
         c->children.clear();
+        for (zpq_blockset *bs : c->sets) {
+            if (bs->slots) (void)hipFree(bs->slots);
+            bs->slots = nullptr;
+            bs->ctx = nullptr;
+        }
+        c->sets.clear();
+        c->set_bytes = 0;
     }
     for (auto &kv : c->models) { (void)hipFree(kv.second.d_model); (void)hipFree(kv.second.d_img); }
     c->slots.release();
@@ -314,7 +340,7 @@ extern "C" int zpq_ctx_set_max_block_bytes(zpq_ctx *c, uint64_t bytes) try
     if (!ctx_live(c)) return ZPQ_E_ARG;
     return set_max_block_bytes(c, bytes);
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
-static int set_max_block_bytes(zpq_ctx *c, uint64_t bytes)
+static uint32_t line_store_cap(const zpq_ctx *c, uint64_t bytes)
 {
     // A block of N bytes (+ PP byte) probes each hash table 2(N+1) times (predictor.v:558-560: once per nibble),
     // so it touches at most that many 64-byte lines.  The store holds sparse_pct % of that bound: probing is
@@ -323,7 +349,11 @@ static int set_max_block_bytes(zpq_ctx *c, uint64_t bytes)
     uint64_t cap = (probes * c->sparse_pct + 99) / 100 + 16;
     cap = (cap + 3) & ~3ull;
     if (cap > (1ull << 25)) cap = 1ull << 25;               // line offsets are 32-bit in the kernel
-    c->sparse_cap = (uint32_t)cap;
+    return (uint32_t)cap;
+}
+static int set_max_block_bytes(zpq_ctx *c, uint64_t bytes)
+{
+    c->sparse_cap = line_store_cap(c, bytes);
     return ZPQ_OK;
 }
 extern "C" int zpq_ctx_last_slots(const zpq_ctx *c) { return ctx_live(c) ? c->last_slots : 0; }
@@ -383,7 +413,7 @@ struct Plan {
 // resident slots / grid of the chain kernel for one slot layout
 static int plan_chain(zpq_ctx *c, const DModel &M, int nblocks, int *nslots_out, int *grid_out, int *bpw_out)
 {
-    const uint64_t max_by_mem = M.slot_bytes ? (c->budget / M.slot_bytes) : (uint64_t)nblocks;
+    const uint64_t max_by_mem = M.slot_bytes ? (c->pool_budget() / M.slot_bytes) : (uint64_t)nblocks;
     if (max_by_mem == 0) return ZPQ_E_NOMEM;
     int bpw = 0;
     const uint64_t can_hold = max_by_mem < (uint64_t)nblocks ? max_by_mem : (uint64_t)nblocks;
@@ -442,7 +472,7 @@ static int plan_batch(zpq_ctx *c, const zpq_model *m, uint32_t flags, int nblock
         }
     } else {
         const DModel &M = *P->M;
-        const uint64_t max_by_mem = M.slot_bytes ? (c->budget / M.slot_bytes) : (uint64_t)nblocks;
+        const uint64_t max_by_mem = M.slot_bytes ? (c->pool_budget() / M.slot_bytes) : (uint64_t)nblocks;
         if (max_by_mem == 0 && !own_slot) return ZPQ_E_NOMEM;
         nslots = nblocks;
         P->gpipe = P->lanes && !decode && zpq_gpipe_applies(&M) != 0;
@@ -1111,6 +1141,290 @@ extern "C" int zpq_block_decode_segment(zpq_block *b, const uint8_t *in, size_t 
     if (final_code) *final_code = code;
     if (first_byte) *first_byte = first;
     return st;
+} ZPQ_CATCH(return ZPQ_E_INTERNAL)
+
+// ------------------------------------------------------------------ N blocks, many segments
+// Predictor.init's fill of one chain-model slot, in the form k_chain<..., KEEP> loads: ICM cm[] = cminit, ISSE weight pairs,
+// MIX2 weights 32768 (predictor.v:366-368,396,443-445); everything else was zeroed before.  One workgroup per slot.
+__global__ void __launch_bounds__(256) k_set_fill(const DModel *Mp, const uint32_t *img, uint8_t *slots)
+{
+    const DModel &M = *Mp;
+    uint8_t *slot = slots + (uint64_t)blockIdx.x * M.slot_bytes;
+    for (int ci = 0; ci < M.n; ci++) {
+        const DComp &c = M.comp[ci];
+        if (c.cm_len && c.cm_fill == ZF_PATTERN) {
+            uint32_t *cm = reinterpret_cast<uint32_t *>(slot + c.cm_off);
+            for (uint32_t i = threadIdx.x; i < c.cm_len; i += 256) cm[i] = img[c.cm_fill_val + i % c.cm_pat_len];
+        }
+        if (c.a16_len && c.a16_fill) {
+            uint16_t *a16 = reinterpret_cast<uint16_t *>(slot + c.a16_off);
+            for (uint32_t i = threadIdx.x; i < c.a16_len; i += 256) a16[i] = (uint16_t)c.a16_fill;
+        }
+    }
+}
+
+// the layout a set of this model gets: the line store wherever a table is larger than a store sized for max_member_bytes
+// (the slots are the set's for its whole life, so the smaller slot always pays), unless ZPQ_SPARSE_MODE=never
+static bool set_layout(const zpq_ctx *c, const zpq_model *m, uint64_t max_member_bytes, DModel *layout, uint32_t *sp)
+{
+    *sp = 0;
+    const bool chain = m->d.fast_kind && zpq_chain_blocks_per_wg(&m->d) > 0;
+    if (!chain) { *layout = m->d; return false; }
+    const char *ev = getenv("ZPQ_SPARSE_FORCE_LOG2");
+    const int lg = ev ? atoi(ev) : 0;
+    const uint32_t cap = (lg >= 8 && lg <= 25) ? (1u << lg) : (max_member_bytes ? line_store_cap(c, max_member_bytes) : c->sparse_cap);
+    const char *mode = getenv("ZPQ_SPARSE_MODE");
+    const bool never = mode && !strcmp(mode, "never");
+    if (!never && zpq_sparse_layout(m->d, cap, layout) && zpq_chain_blocks_per_wg(layout) > 0) *sp = cap;
+    else *layout = m->d;
+    return true;
+}
+
+static int set_capacity(zpq_ctx *c, const DModel &layout, bool chain)
+{
+    const uint64_t by_mem = layout.slot_bytes ? c->pool_budget() / layout.slot_bytes : (1u << 20);
+    const uint64_t resident = chain ? (uint64_t)zpq_chain_max_wgs(&layout, c->cus) * (uint64_t)zpq_chain_blocks_per_wg(&layout)
+                                    : (uint64_t)c->cus * (uint64_t)zpq_generic_blocks_per_cu(&layout);
+    const uint64_t n = by_mem < resident ? by_mem : resident;
+    return n > (1u << 20) ? (1 << 20) : (int)n;
+}
+
+extern "C" int zpq_blockset_capacity(zpq_ctx *c, const zpq_model *m, uint64_t max_member_bytes) try
+{
+    if (!ctx_live(c)) return c ? ZPQ_E_CLOSED : ZPQ_E_ARG;
+    if (!m) return ZPQ_E_ARG;
+    HIPCK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mu);
+    static thread_local DModel layout;
+    uint32_t sp = 0;
+    const bool chain = set_layout(c, m, max_member_bytes, &layout, &sp);
+    return set_capacity(c, layout, chain);
+} ZPQ_CATCH(return ZPQ_E_INTERNAL)
+
+extern "C" int zpq_blockset_create(zpq_ctx *c, const zpq_model *m, int nmembers, uint64_t max_member_bytes, zpq_blockset **out) try
+{
+    if (!out) return ZPQ_E_ARG;
+    *out = nullptr;
+    if (!ctx_live(c)) return c ? ZPQ_E_CLOSED : ZPQ_E_ARG;
+    if (!m || nmembers < 1) return ZPQ_E_ARG;
+    HIPCK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mu);
+    zpq_blockset *s = new (std::nothrow) zpq_blockset();
+    if (!s) return ZPQ_E_NOMEM;
+    s->chain = set_layout(c, m, max_member_bytes, &s->layout, &s->sp);
+    s->nmembers = nmembers;
+    s->bytes = (uint64_t)nmembers * s->layout.slot_bytes + 256;
+    if (nmembers > set_capacity(c, s->layout, s->chain) || s->bytes > c->pool_budget()) { delete s; return ZPQ_E_NOMEM; }
+    if (hipMalloc((void **)&s->slots, s->bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(c->stream);
+        c->slots.release();                                 // the idle slot pool makes room; it grows back on demand
+        if (hipMalloc((void **)&s->slots, s->bytes) != hipSuccess) { (void)hipGetLastError(); delete s; return ZPQ_E_NOMEM; }
+    }
+    int rc = ZPQ_OK;
+    if (s->chain) {
+        DevModel dm;
+        rc = get_dev_model(c, m, s->layout, s->sp, &dm);
+        if (rc == ZPQ_OK && hipMemset2DAsync(s->slots, s->layout.slot_bytes, 0, s->layout.zero_bytes, (size_t)nmembers, c->stream) != hipSuccess) rc = ZPQ_E_NODEVICE;
+        if (rc == ZPQ_OK) {
+            hipLaunchKernelGGL(k_set_fill, dim3(nmembers), dim3(256), 0, c->stream, (const DModel *)dm.d_model, (const uint32_t *)dm.d_img, s->slots);
+            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = ZPQ_E_NODEVICE;
+        }
+    }
+    if (rc != ZPQ_OK) { (void)hipGetLastError(); (void)hipFree(s->slots); delete s; return rc; }
+    s->failed.assign((size_t)nmembers, ZPQ_OK);
+    s->fresh.assign((size_t)nmembers, 1);
+    s->ctx = c; s->model = m;
+    {
+        std::lock_guard<std::mutex> lk2(g_reg_mu);
+        if (!live_set().count(c)) { (void)hipFree(s->slots); delete s; return ZPQ_E_CLOSED; }
+        c->sets.push_back(s);
+        c->set_bytes += s->bytes;
+    }
+    zpq_model_retain(m);
+    *out = s;
+    return ZPQ_OK;
+} ZPQ_CATCH(return ZPQ_E_INTERNAL)
+
+extern "C" void zpq_blockset_destroy(zpq_blockset *s) try
+{
+    if (!s) return;
+    zpq_ctx *c = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_reg_mu);
+        c = s->ctx;                                         // nullptr: the ctx went first and took the slots with it
+        if (c) {
+            c->sets.erase(std::remove(c->sets.begin(), c->sets.end(), s), c->sets.end());
+            c->set_bytes -= s->bytes;
+        }
+        s->ctx = nullptr;
+    }
+    if (c) {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+        if (s->slots) (void)hipFree(s->slots);
+    }
+    zpq_model_release(s->model);
+    delete s;
+} ZPQ_CATCH(return)
+
+static int set_segments(zpq_blockset *s, int decode, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
+                        uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, uint32_t *consumed,
+                        uint32_t *final_code, uint32_t *first_byte, int32_t *status)
+{
+    if (!s) return ZPQ_E_ARG;
+    zpq_ctx *c = s->ctx;
+    if (!c) return ZPQ_E_CLOSED;
+    if (!ctx_live(c)) return ZPQ_E_CLOSED;
+    if (n < 0 || n > s->nmembers || (flags & ZPQ_FLAG_NOEOF)) return ZPQ_E_ARG;
+    if (n == 0) return ZPQ_OK;
+    if (!in_off || !out_off || !out_len || !status) return ZPQ_E_ARG;
+    for (int b = 0; b < n; b++)
+        if (in_off[b + 1] < in_off[b] || out_off[b + 1] < out_off[b] ||
+            in_off[b + 1] - in_off[b] > 0xFFFFFFF0ull || out_off[b + 1] - out_off[b] > 0xFFFFFFF0ull)
+            return ZPQ_E_ARG;
+    if ((in_off[n] > in_off[0] && !in) || (out_off[n] > out_off[0] && !out)) return ZPQ_E_ARG;
+    std::vector<int32_t> mem((size_t)n);
+    {
+        std::vector<uint8_t> seen((size_t)s->nmembers, 0);
+        for (int i = 0; i < n; i++) {
+            const int32_t k = member ? member[i] : i;
+            if (k < 0 || k >= s->nmembers || seen[(size_t)k]) return ZPQ_E_ARG;
+            seen[(size_t)k] = 1;
+            mem[(size_t)i] = k;
+        }
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCK(hipSetDevice(c->device));
+    // failed members report their status and take no part; the rest are packed into one batch
+    std::vector<int> live;
+    for (int i = 0; i < n; i++) {
+        const int32_t f = s->failed[(size_t)mem[(size_t)i]];
+        if (f != ZPQ_OK) {
+            status[i] = f; out_len[i] = 0;
+            if (consumed) consumed[i] = 0;
+            if (final_code) final_code[i] = 0;
+            if (first_byte) first_byte[i] = 0xFFFFFFFFu;
+        } else live.push_back(i);
+    }
+    const int k = (int)live.size();
+    if (k == 0) return ZPQ_OK;
+    const bool all = k == n;
+    std::vector<uint64_t> h_in((size_t)k + 1), h_out((size_t)k + 1);
+    std::vector<int32_t> h_map((size_t)k);
+    h_in[0] = 0; h_out[0] = 0;
+    for (int j = 0; j < k; j++) {
+        const int i = live[(size_t)j];
+        // (16-byte aligned slabs: the kernels read and write them by dwords)
+        h_in[(size_t)j + 1] = all ? in_off[i + 1] - in_off[0] : h_in[(size_t)j] + (in_off[i + 1] - in_off[i]);
+        h_out[(size_t)j + 1] = all ? out_off[i + 1] - out_off[0] : h_out[(size_t)j] + (out_off[i + 1] - out_off[i]);
+        h_map[(size_t)j] = mem[(size_t)i];
+    }
+    const size_t in_bytes = (size_t)h_in[(size_t)k], out_bytes = (size_t)h_out[(size_t)k];
+    const size_t offb = (size_t)(k + 1) * 8, u32b = (size_t)k * 4;
+    int rc;
+    if ((rc = c->s_in.ensure(in_bytes + 16)) || (rc = c->s_out.ensure(out_bytes + 16)) || (rc = c->s_inoff.ensure(offb)) ||
+        (rc = c->s_outoff.ensure(offb)) || (rc = c->s_status.ensure(u32b)) || (rc = c->s_misc.ensure(u32b + 16)))
+        return rc;
+    for (auto &b : c->s_u32) if ((rc = b.ensure(u32b))) return rc;
+    hipStream_t st = c->stream;
+    if (all) { if (in_bytes) HIPCK(hipMemcpyAsync(c->s_in.p, in + in_off[0], in_bytes, hipMemcpyHostToDevice, st)); }
+    else for (int j = 0; j < k; j++) {
+        const int i = live[(size_t)j];
+        const size_t len = (size_t)(in_off[i + 1] - in_off[i]);
+        if (len) HIPCK(hipMemcpyAsync((uint8_t *)c->s_in.p + h_in[(size_t)j], in + in_off[i], len, hipMemcpyHostToDevice, st));
+    }
+    HIPCK(hipMemcpyAsync(c->s_inoff.p, h_in.data(), offb, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(c->s_outoff.p, h_out.data(), offb, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(c->s_misc.p, h_map.data(), u32b, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemsetAsync(c->s_status.p, 0xff, u32b, st));   // -1: "kernel never reported"
+    HIPCK(hipMemsetAsync(c->s_u32[0].p, 0, u32b, st));
+    uint32_t *d_len = (uint32_t *)c->s_u32[0].p, *d_cons = (uint32_t *)c->s_u32[1].p, *d_code = (uint32_t *)c->s_u32[2].p,
+             *d_first = (uint32_t *)c->s_u32[3].p;
+    if (s->chain) {
+        DevModel dm;
+        if ((rc = get_dev_model(c, s->model, s->layout, s->sp, &dm)) != ZPQ_OK) return rc;
+        DBatch B;
+        memset(&B, 0, sizeof B);
+        B.model = dm.d_model; B.img = dm.d_img;
+        B.slots = s->slots; B.nslots = k; B.nblocks = k;
+        B.flags = (flags & 0xffu & ~(uint32_t)(ZPQ_FLAG_GENERIC | ZPQ_FLAG_LANES)) | ZB_KEEP_STATE;
+        B.in = (const uint8_t *)c->s_in.p; B.in_off = (const uint64_t *)c->s_inoff.p;
+        B.out = (uint8_t *)c->s_out.p; B.out_off = (const uint64_t *)c->s_outoff.p;
+        B.out_len = d_len; B.status = (int32_t *)c->s_status.p;
+        if (decode) { B.consumed = d_cons; B.final_code = d_code; B.first_byte = d_first; }
+        B.squash = c->d_squash; B.stretch = c->d_stretch; B.dt = c->d_dt; B.dt2k = c->d_dt2k;
+        B.ns = c->d_ns; B.stretch_c = c->d_stretch_c;
+        B.slot_map = (const int32_t *)c->s_misc.p;
+        int bpw = 0;
+        if (!zpq_chain_plan(&s->layout, k, c->cus, &bpw)) return ZPQ_E_INTERNAL;
+        const int grid = (k + bpw - 1) / bpw;
+        if (grid > zpq_chain_max_wgs(&s->layout, c->cus)) return ZPQ_E_INTERNAL;   // (nmembers <= capacity rules this out)
+        c->last_slots = k;
+        c->last_sp = s->sp;
+        HIPCK(hipEventRecord(c->ev0, st));
+        const char *name = nullptr;
+        if ((rc = zpq_launch_chain(&B, &s->layout, decode, grid, bpw, st, &name)) != ZPQ_OK) return rc;
+        c->last_name = name;
+        HIPCK(hipGetLastError());
+        HIPCK(hipEventRecord(c->ev1, st));
+        c->ev_valid = true;
+    } else {
+        // other models: the lane-0 kernel on the member's slot, one launch each (ZB_KEEP_STATE from the second segment on)
+        for (int j = 0; j < k; j++) {
+            const int32_t mb = h_map[(size_t)j];
+            BatchArgs a;
+            memset(&a, 0, sizeof a);
+            a.nblocks = 1; a.in = (const uint8_t *)c->s_in.p; a.in_off = (const uint64_t *)c->s_inoff.p + j;
+            a.flags = (flags & 0xffu) | ZPQ_FLAG_GENERIC | (s->fresh[(size_t)mb] ? 0u : ZB_KEEP_STATE);
+            a.out = (uint8_t *)c->s_out.p; a.out_off = (const uint64_t *)c->s_outoff.p + j; a.out_len = d_len + j;
+            if (decode) { a.consumed = d_cons + j; a.final_code = d_code + j; a.first_byte = d_first + j; }
+            a.status = (int32_t *)c->s_status.p + j;
+            a.own_slot = s->slots + (uint64_t)mb * s->layout.slot_bytes;
+            if ((rc = run_batch(c, s->model, decode, a)) != ZPQ_OK) { (void)hipStreamSynchronize(st); return rc; }
+        }
+    }
+    std::vector<uint32_t> r_len((size_t)k), r_cons((size_t)k), r_code((size_t)k), r_first((size_t)k);
+    std::vector<int32_t> r_st((size_t)k);
+    HIPCK(hipMemcpyAsync(r_len.data(), d_len, u32b, hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(r_st.data(), c->s_status.p, u32b, hipMemcpyDeviceToHost, st));
+    if (decode) {
+        HIPCK(hipMemcpyAsync(r_cons.data(), d_cons, u32b, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(r_code.data(), d_code, u32b, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(r_first.data(), d_first, u32b, hipMemcpyDeviceToHost, st));
+    }
+    if (all && out_bytes) HIPCK(hipMemcpyAsync(out + out_off[0], c->s_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    for (int j = 0; j < k; j++) {
+        const int i = live[(size_t)j];
+        const int32_t mb = h_map[(size_t)j];
+        out_len[i] = r_len[(size_t)j]; status[i] = r_st[(size_t)j];
+        if (decode && consumed) consumed[i] = r_cons[(size_t)j];
+        if (decode && final_code) final_code[i] = r_code[(size_t)j];
+        if (decode && first_byte) first_byte[i] = r_first[(size_t)j];
+        s->fresh[(size_t)mb] = 0;
+        if (r_st[(size_t)j] != ZPQ_OK) s->failed[(size_t)mb] = r_st[(size_t)j];
+        if (!all) {
+            const uint64_t cap = out_off[i + 1] - out_off[i];
+            const size_t got = (size_t)(r_len[(size_t)j] < cap ? r_len[(size_t)j] : cap);
+            if (got) HIPCK(hipMemcpyAsync(out + out_off[i], (uint8_t *)c->s_out.p + h_out[(size_t)j], got, hipMemcpyDeviceToHost, st));
+        }
+    }
+    if (!all) HIPCK(hipStreamSynchronize(st));
+    return ZPQ_OK;
+}
+
+extern "C" int zpq_blockset_encode_segments(zpq_blockset *s, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
+                                            uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status) try
+{
+    return set_segments(s, 0, n, member, in, in_off, flags, out, out_off, out_len, nullptr, nullptr, nullptr, status);
+} ZPQ_CATCH(return ZPQ_E_INTERNAL)
+
+extern "C" int zpq_blockset_decode_segments(zpq_blockset *s, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
+                                            uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, uint32_t *consumed,
+                                            uint32_t *final_code, uint32_t *first_byte, int32_t *status) try
+{
+    return set_segments(s, 1, n, member, in, in_off, flags, out, out_off, out_len, consumed, final_code, first_byte, status);
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 // ------------------------------------------------------------------ test hooks

@@ -121,9 +121,10 @@ struct Piece {
 
 static int add_pieces(zpq_ctx *ctx, int level, const std::vector<Piece> &files, std::vector<uint8_t> *archive, std::vector<size_t> *ends);
 
-int archive_add(zpq_ctx *ctx, int level, const std::vector<ArchiveFile> &files, std::vector<uint8_t> *archive, size_t fragment_bytes)
+int archive_add(zpq_ctx *ctx, int level, const std::vector<ArchiveFile> &files, std::vector<uint8_t> *archive, size_t fragment_bytes,
+                int solid_files)
 {
-    return archive_add(std::vector<zpq_ctx *>{ctx}, level, files, archive, fragment_bytes);
+    return archive_add(std::vector<zpq_ctx *>{ctx}, level, files, archive, fragment_bytes, solid_files);
 }
 
 // Several GPUs: block b -> context b mod G, one host thread per context, no collective; the
@@ -137,24 +138,25 @@ static void cut_pieces(std::vector<Piece> &pieces, const std::string &name, cons
     }
 }
 static int add_all(const std::vector<zpq_ctx *> &ctxs, int level, const std::vector<Piece> &pieces, std::vector<uint8_t> *archive);
+static int add_solid(const std::vector<zpq_ctx *> &ctxs, int level, const std::vector<Piece> &pieces, int solid, std::vector<uint8_t> *archive);
 
 int archive_add(const std::vector<zpq_ctx *> &ctxs, int level, const std::vector<ArchiveFile> &files, std::vector<uint8_t> *archive,
-                size_t fragment_bytes)
+                size_t fragment_bytes, int solid_files)
 {
-    if (!archive || level < 0 || level > 5 || ctxs.empty()) return ZPQ_E_ARG;
+    if (!archive || level < 0 || level > 5 || ctxs.empty() || solid_files < 0) return ZPQ_E_ARG;
     std::vector<Piece> pieces;
     for (const ArchiveFile &f : files) cut_pieces(pieces, f.name, f.comment, f.data.data(), f.data.size(), fragment_bytes);
-    return add_all(ctxs, level, pieces, archive);
+    return solid_files > 1 ? add_solid(ctxs, level, pieces, solid_files, archive) : add_all(ctxs, level, pieces, archive);
 }
 
 // the same over caller-owned bytes (no copy of the file contents is made on the way to the GPU)
 int archive_add_views(const std::vector<zpq_ctx *> &ctxs, int level, int nfiles, const char *const *names, const char *const *comments,
-                      const uint8_t *const *data, const uint64_t *lens, std::vector<uint8_t> *archive, size_t fragment_bytes)
+                      const uint8_t *const *data, const uint64_t *lens, std::vector<uint8_t> *archive, size_t fragment_bytes, int solid_files)
 {
-    if (!archive || level < 0 || level > 5 || ctxs.empty() || nfiles < 0) return ZPQ_E_ARG;
+    if (!archive || level < 0 || level > 5 || ctxs.empty() || nfiles < 0 || solid_files < 0) return ZPQ_E_ARG;
     std::vector<Piece> pieces;
     for (int i = 0; i < nfiles; i++) cut_pieces(pieces, names[i], comments[i], data[i], (size_t)lens[i], fragment_bytes);
-    return add_all(ctxs, level, pieces, archive);
+    return solid_files > 1 ? add_solid(ctxs, level, pieces, solid_files, archive) : add_all(ctxs, level, pieces, archive);
 }
 
 static int add_all(const std::vector<zpq_ctx *> &ctxs, int level, const std::vector<Piece> &pieces, std::vector<uint8_t> *archive)
@@ -331,6 +333,177 @@ static int add_pieces(zpq_ctx *ctx, int level, const std::vector<Piece> &files, 
     });
     if (ends) for (int i = 0; i < n; i++) ends->push_back(at[i + 1]);
     (void)w;
+    return ZPQ_OK;
+}
+
+// ------------------------------------------------------------------ add, several files per block (NOT reference behaviour)
+// solid = N > 1: N consecutive pieces share one block, a segment each with its own name, comment and SHA-1 -- the
+// layout the reference's extractor reads (it loops find_filename inside a block, cmd/main.v:349-380) and its writer
+// never makes.  The model carries over from file to file (compressor.v:238-245), so small files stop paying for a fresh
+// model, a block header and a slot clear each.  Blocks are independent: they go through block sets (zpq_blockset_*),
+// round r of a set coding the r-th piece of every block of the set in one launch.
+namespace {
+typedef std::vector<Piece> SolidBlock;
+
+// one block through the sequential front end (level 0: no coder; or a block whose set member failed)
+int solid_block_sequential(zpq_ctx *ctx, int level, const SolidBlock &blk, std::vector<uint8_t> *out)
+{
+    VecWriter w(out);
+    Compressor c(level == 0 ? nullptr : ctx);
+    c.set_output(&w);
+    c.start_block(level);
+    for (const Piece &f : blk) {
+        FileReader r(std::vector<uint8_t>(f.p, f.p + f.n));
+        c.start_segment(f.name, f.comment);
+        c.set_input(&r);
+        while (c.compress(65536)) {}
+        c.end_segment();
+        if (c.last_error() != ZPQ_OK) return c.last_error();
+    }
+    c.end_block();
+    return c.last_error();
+}
+
+// this context's blocks, appended to *out in their order; ends[k] = size of *out behind block k
+int add_solid_blocks(zpq_ctx *ctx, int level, const std::vector<const SolidBlock *> &blocks, std::vector<uint8_t> *out, std::vector<size_t> *ends)
+{
+    const int nb = (int)blocks.size();
+    if (level == 0) {
+        for (const SolidBlock *b : blocks) {
+            const int rc = solid_block_sequential(nullptr, 0, *b, out);
+            if (rc != ZPQ_OK) return rc;
+            ends->push_back(out->size());
+        }
+        return ZPQ_OK;
+    }
+    if (!ctx) return ZPQ_E_NODEVICE;
+    uint8_t hdr[256];
+    int hlen = 0, cend = 0, hbegin = 0, hend = 0;
+    int rc = zpq_level_header(level, hdr, (int)sizeof hdr, &hlen, &cend, &hbegin, &hend);
+    if (rc != ZPQ_OK) return rc;
+    zpq_model *model = nullptr;
+    if ((rc = zpq_model_create(hdr, hlen, cend, hbegin, hend, &model)) != ZPQ_OK) return rc;
+    struct ModelGuard { zpq_model *m; ~ModelGuard() { zpq_model_destroy(m); } } guard{model};
+    std::vector<uint8_t> head;
+    { VecWriter hw(&head); framing::block_header(hw, hdr, hlen, cend, hbegin, hend); }
+
+    std::vector<std::vector<std::vector<uint8_t>>> coded((size_t)nb);      // [block][piece] payload
+    std::vector<uint8_t> failed((size_t)nb, 0);
+    for (int b0 = 0; b0 < nb;) {
+        // a set of as many blocks as one may hold, its line store sized for the largest member's real sum (every segment
+        // codes a PP byte of its own)
+        uint64_t maxsum = 0;
+        int b1 = b0;
+        int cap_members = 1;
+        for (; b1 < nb; b1++) {
+            uint64_t sum = blocks[(size_t)b1]->size();
+            for (const Piece &f : *blocks[(size_t)b1]) { if (f.n > 0xFFFFFF00ull) return ZPQ_E_TOOBIG; sum += f.n; }
+            const uint64_t m2 = std::max(maxsum, sum);
+            int capn = cap_members;
+            if (b1 == b0 || m2 != maxsum) capn = zpq_blockset_capacity(ctx, model, m2);   // (a larger store: fewer members fit)
+            if (capn < 0) return capn;
+            if (capn < 1) return ZPQ_E_NOMEM;
+            if (b1 - b0 + 1 > capn) break;
+            maxsum = m2; cap_members = capn;
+        }
+        if (b1 == b0) return ZPQ_E_NOMEM;
+        const int nm = b1 - b0;
+        zpq_blockset *set = nullptr;
+        if ((rc = zpq_blockset_create(ctx, model, nm, maxsum, &set)) != ZPQ_OK) return rc;
+        struct SetGuard { zpq_blockset *s; ~SetGuard() { zpq_blockset_destroy(s); } } sguard{set};
+        size_t rounds = 0;
+        for (int b = b0; b < b1; b++) { rounds = std::max(rounds, blocks[(size_t)b]->size()); coded[(size_t)b].resize(blocks[(size_t)b]->size()); }
+        std::vector<uint8_t> in, outbuf;
+        for (size_t r = 0; r < rounds; r++) {
+            std::vector<int32_t> member;
+            std::vector<uint64_t> in_off(1, 0), out_off(1, 0);
+            for (int b = b0; b < b1; b++) {
+                if (blocks[(size_t)b]->size() <= r || failed[(size_t)b]) continue;
+                const Piece &f = (*blocks[(size_t)b])[r];
+                member.push_back(b - b0);
+                in_off.push_back(in_off.back() + f.n);
+                out_off.push_back(out_off.back() + ((f.n + f.n / 4 + 1024 + 15) & ~(uint64_t)15));
+            }
+            const int k = (int)member.size();
+            if (!k) continue;
+            in.resize((size_t)in_off.back() + 16);
+            outbuf.resize((size_t)out_off.back() + 16);
+            parallel_for(k, in_off.back(), [&](int j) {
+                const Piece &f = (*blocks[(size_t)(b0 + member[(size_t)j])])[r];
+                if (f.n) memcpy(in.data() + in_off[(size_t)j], f.p, f.n);
+            });
+            std::vector<uint32_t> len((size_t)k);
+            std::vector<int32_t> st((size_t)k);
+            // compress() is always entered, so every segment codes its PP byte first (compressor.v:271-274)
+            if ((rc = zpq_blockset_encode_segments(set, k, member.data(), in.data(), in_off.data(), ZPQ_FLAG_PP, outbuf.data(), out_off.data(),
+                                                   len.data(), st.data())) != ZPQ_OK)
+                return rc;
+            for (int j = 0; j < k; j++) {
+                const int b = b0 + member[(size_t)j];
+                if (st[(size_t)j] != ZPQ_OK) { failed[(size_t)b] = 1; continue; }   // (a payload that outgrew its slab, ...): redone below
+                coded[(size_t)b][r].assign(outbuf.data() + out_off[(size_t)j], outbuf.data() + out_off[(size_t)j] + len[(size_t)j]);
+            }
+        }
+        b0 = b1;
+    }
+    // digests on a few host threads, then the framing: [locator + header | per file: segment header, payload, trailer | FF]
+    std::vector<std::pair<int, int>> all;
+    uint64_t total = 0;
+    for (int b = 0; b < nb; b++) for (size_t r = 0; r < blocks[(size_t)b]->size(); r++) { all.emplace_back(b, (int)r); total += (*blocks[(size_t)b])[r].n; }
+    std::vector<uint8_t> sha(all.size() * 20);
+    parallel_for((int)all.size(), total, [&](int i) { const Piece &f = (*blocks[(size_t)all[(size_t)i].first])[(size_t)all[(size_t)i].second]; host_sha1(f.p, f.n, &sha[(size_t)i * 20]); });
+    size_t si = 0;
+    for (int b = 0; b < nb; b++) {
+        const SolidBlock &blk = *blocks[(size_t)b];
+        if (failed[(size_t)b]) {
+            if ((rc = solid_block_sequential(ctx, level, blk, out)) != ZPQ_OK) return rc;
+            si += blk.size();
+        } else {
+            out->insert(out->end(), head.begin(), head.end());
+            for (size_t r = 0; r < blk.size(); r++, si++) {
+                out->push_back(1);                                                  // framing::segment_header
+                out->insert(out->end(), blk[r].name.begin(), blk[r].name.end());
+                out->push_back(0);
+                out->insert(out->end(), blk[r].comment.begin(), blk[r].comment.end());
+                out->push_back(0); out->push_back(0);
+                out->insert(out->end(), coded[(size_t)b][r].begin(), coded[(size_t)b][r].end());
+                const uint8_t tr[5] = {0, 0, 0, 0, 253};                           // framing::segment_trailer
+                out->insert(out->end(), tr, tr + 5);
+                out->insert(out->end(), sha.begin() + (ptrdiff_t)(si * 20), sha.begin() + (ptrdiff_t)(si * 20 + 20));
+            }
+            out->push_back(0xFF);                                                   // framing::block_end
+        }
+        ends->push_back(out->size());
+    }
+    return ZPQ_OK;
+}
+}  // namespace
+
+static int add_solid(const std::vector<zpq_ctx *> &ctxs, int level, const std::vector<Piece> &pieces, int solid, std::vector<uint8_t> *archive)
+{
+    std::vector<SolidBlock> blocks;
+    for (size_t i = 0; i < pieces.size(); i += (size_t)solid)
+        blocks.emplace_back(pieces.begin() + (ptrdiff_t)i, pieces.begin() + (ptrdiff_t)std::min(pieces.size(), i + (size_t)solid));
+    if (blocks.empty()) return ZPQ_OK;
+    // block g -> context g mod G, one host thread per context; written out in their original order
+    const size_t G = level == 0 ? 1 : std::min(ctxs.size(), blocks.size());
+    std::vector<std::vector<const SolidBlock *>> shard(G);
+    for (size_t g = 0; g < blocks.size(); g++) shard[g % G].push_back(&blocks[g]);
+    std::vector<std::vector<uint8_t>> outs(G);
+    std::vector<std::vector<size_t>> ends(G);
+    std::vector<int> rcs(G, ZPQ_OK);
+    if (G == 1) rcs[0] = add_solid_blocks(ctxs[0], level, shard[0], &outs[0], &ends[0]);
+    else {
+        std::vector<std::thread> th;
+        for (size_t g = 0; g < G; g++) th.emplace_back([&, g]() { rcs[g] = add_solid_blocks(ctxs[g], level, shard[g], &outs[g], &ends[g]); });
+        for (std::thread &t : th) t.join();
+    }
+    for (int r : rcs) if (r != ZPQ_OK) return r;
+    for (size_t i = 0; i < blocks.size(); i++) {
+        const size_t g = i % G, k = i / G;
+        const size_t from = k ? ends[g][k - 1] : 0;
+        archive->insert(archive->end(), outs[g].begin() + (ptrdiff_t)from, outs[g].begin() + (ptrdiff_t)ends[g][k]);
+    }
     return ZPQ_OK;
 }
 
@@ -523,11 +696,17 @@ int archive_extract(const std::vector<zpq_ctx *> &ctxs, const uint8_t *arc, size
 }
 
 namespace {
-struct Decoded { bool done = false; size_t end = 0; ArchiveFile f; };
+struct Decoded {
+    bool done = false; size_t end = 0; ArchiveFile f;
+    bool multi = false;                  // the first segment decoded cleanly and another segment follows it: a candidate for the sets
+    std::vector<ArchiveFile> more;       // segments 2.. of a block that went through a set
+};
 typedef std::map<std::vector<uint8_t>, std::vector<int>> Groups;
 }  // namespace
 static int decode_groups(zpq_ctx *ctx, const uint8_t *arc, size_t n, bool want_data, const std::vector<BlockRec> &blocks,
                          const Groups &groups, std::vector<Decoded> &dec);
+static int decode_multi(zpq_ctx *ctx, const uint8_t *arc, size_t n, bool want_data, const std::vector<BlockRec> &blocks,
+                        const Groups &groups, std::vector<Decoded> &dec);
 
 static int extract_segments(const std::vector<zpq_ctx *> &ctxs, const uint8_t *arc, size_t n, bool want_data, std::vector<ArchiveFile> *files)
 {
@@ -569,6 +748,23 @@ static int extract_segments(const std::vector<zpq_ctx *> &ctxs, const uint8_t *a
             for (std::thread &t : th) t.join();
         }
         for (int r : rcs) if (r != ZPQ_OK) return r;
+        // ---- pass 2b: blocks that hold several segments, all blocks of one header through block sets, round r decoding the
+        //      r-th segment of every block in one launch (the first segment again: the set's state must see it).  A block
+        //      that is unusual in any way is left to the sequential replay below, with the result it always had.
+        std::vector<Groups> multi(G);
+        size_t nmulti = 0;
+        for (size_t i = 0; i < blocks.size(); i++) if (dec[i].multi && !dec[i].done) multi[nmulti++ % G][blocks[i].hdr].push_back((int)i);
+        if (nmulti) {
+            std::fill(rcs.begin(), rcs.end(), ZPQ_OK);
+            if (G == 1 || nmulti < 2) rcs[0] = decode_multi(ctxs[0], arc, n, want_data, blocks, multi[0], dec);
+            else {
+                std::vector<std::thread> th;
+                for (size_t g = 0; g < G; g++)
+                    th.emplace_back([&, g]() { rcs[g] = decode_multi(ctxs[g], arc, n, want_data, blocks, multi[g], dec); });
+                for (std::thread &t : th) t.join();
+            }
+            for (int r : rcs) if (r != ZPQ_OK) return r;
+        }
     }
     // ---- everything else, in archive order, following the sequential reader: `seq` is where it stands.
     //      A record that begins before `seq` lies inside the block just consumed (the reference never sees it);
@@ -591,6 +787,7 @@ static int extract_segments(const std::vector<zpq_ctx *> &ctxs, const uint8_t *a
         if (dec[i].done) {
             const bool clean = dec[i].f.sha1_ok && dec[i].f.status == ZPQ_OK;
             files->push_back(std::move(dec[i].f));
+            for (ArchiveFile &f : dec[i].more) files->push_back(std::move(f));     // (a block from a set: every segment was clean)
             seq = clean ? dec[i].end : tag + 1;
             continue;
         }
@@ -715,7 +912,12 @@ static int decode_groups(zpq_ctx *ctx, const uint8_t *arc, size_t n, bool want_d
                         sha_ok = memcmp(arc + p, &sha[(size_t)k * 20], 20) == 0;
                         p += 20;
                     }
-                    if (get() != 0xFF) continue;                                   // more segments (or damage): replay sequentially
+                    const int after = get();
+                    if (after != 0xFF) {
+                        // more segments (or damage): through a block set if all is as a writer leaves it, else replayed sequentially
+                        if (after == 1 && sha_ok && first[k] == 0u) dec[bi].multi = true;
+                        continue;
+                    }
                     Decoded &d = dec[bi];
                     d.done = true;
                     d.end = p;
@@ -732,6 +934,121 @@ static int decode_groups(zpq_ctx *ctx, const uint8_t *arc, size_t n, bool want_d
                         dec[(size_t)todo[k]].f.data.assign(slab + pk_off[k], slab + pk_off[k] + len[k]);
                     });
                 todo.swap(again);
+            }
+        }
+    }
+    return ZPQ_OK;
+}
+
+// one context's share of the multi-segment blocks: per distinct header sets of as many blocks as one may hold
+static int decode_multi(zpq_ctx *ctx, const uint8_t *arc, size_t n, bool want_data, const std::vector<BlockRec> &blocks,
+                        const Groups &groups, std::vector<Decoded> &dec)
+{
+    struct Member {
+        int bi; size_t pos; std::string name, comment; std::vector<ArchiveFile> files; bool alive = true, finished = false; size_t end = 0;
+    };
+    for (const auto &g : groups) {
+        const BlockRec &b0 = blocks[(size_t)g.second[0]];
+        zpq_model *model = nullptr;
+        if (zpq_model_create(b0.hdr.data(), (int)b0.hdr.size(), b0.cend, b0.hbegin, b0.hend, &model) != ZPQ_OK) continue;
+        struct ModelGuard { zpq_model *m; ~ModelGuard() { zpq_model_destroy(m); } } guard{model};
+        for (size_t c0 = 0; c0 < g.second.size();) {
+            // the decoded sizes are not known: the line store is sized for eight times the coded bytes (a member that needs
+            // more gets ZPQ_E_TOOBIG and is replayed sequentially)
+            uint64_t mmb = 0;
+            size_t c1 = c0;
+            int capn = 0;
+            for (; c1 < g.second.size(); c1++) {
+                const BlockRec &b = blocks[(size_t)g.second[c1]];
+                const uint64_t m2 = std::max<uint64_t>(mmb, (uint64_t)(b.next_tag - b.payload) * 8 + 65536);
+                if (c1 == c0 || m2 != mmb) capn = zpq_blockset_capacity(ctx, model, m2);
+                if (capn < 1 || (int)(c1 - c0) + 1 > capn) break;
+                mmb = m2;
+            }
+            if (c1 == c0) { c0++; continue; }                                   // does not fit at all: replayed
+            std::vector<Member> mem;
+            for (size_t c = c0; c < c1; c++) {
+                const BlockRec &b = blocks[(size_t)g.second[c]];
+                Member m;
+                m.bi = g.second[c]; m.pos = b.payload; m.name = b.name; m.comment = b.comment;
+                mem.push_back(std::move(m));
+            }
+            c0 = c1;
+            zpq_blockset *set = nullptr;
+            if (zpq_blockset_create(ctx, model, (int)mem.size(), mmb, &set) != ZPQ_OK) continue;   // replayed
+            struct SetGuard { zpq_blockset *s; ~SetGuard() { zpq_blockset_destroy(s); } } sguard{set};
+            std::vector<uint8_t> out;
+            for (;;) {
+                // the members still going, in archive order: a range may run on to the next member's segment (the decoder
+                // stops at the EOF symbol), so the ranges are contiguous
+                std::vector<int32_t> member;
+                for (size_t j = 0; j < mem.size(); j++) if (mem[j].alive && !mem[j].finished) member.push_back((int32_t)j);
+                const int k = (int)member.size();
+                if (!k) break;
+                std::vector<uint64_t> in_off((size_t)k + 1), out_off((size_t)k + 1, 0);
+                for (int j = 0; j < k; j++) {
+                    const Member &m = mem[(size_t)member[(size_t)j]];
+                    const BlockRec &b = blocks[(size_t)m.bi];
+                    in_off[(size_t)j] = m.pos;
+                    const uint64_t hint = size_hint(m.comment), paylen = b.next_tag - m.pos;
+                    uint64_t cap = paylen * 8 + 65536;
+                    if (hint != ~0ull) cap = std::min<uint64_t>(hint + 64, paylen * 4096 + 65536);
+                    out_off[(size_t)j + 1] = out_off[(size_t)j] + ((cap + 15) & ~15ull);
+                }
+                in_off[(size_t)k] = blocks[(size_t)mem[(size_t)member[(size_t)k - 1]].bi].next_tag;
+                out.resize((size_t)out_off[(size_t)k] + 16);
+                std::vector<uint32_t> meta((size_t)k * 4);
+                std::vector<int32_t> st((size_t)k);
+                uint32_t *len = meta.data(), *cons = len + k, *code = cons + k, *first = code + k;
+                const int rc = zpq_blockset_decode_segments(set, k, member.data(), arc, in_off.data(), ZPQ_FLAG_PP, out.data(), out_off.data(),
+                                                            len, cons, code, first, st.data());
+                if (rc != ZPQ_OK) return rc;
+                std::vector<uint8_t> sha((size_t)k * 20);
+                uint64_t tot = 0;
+                for (int j = 0; j < k; j++) if (st[(size_t)j] == ZPQ_OK) tot += len[j];
+                parallel_for(k, tot, [&](int j) { if (st[(size_t)j] == ZPQ_OK) host_sha1(out.data() + out_off[(size_t)j], len[j], &sha[(size_t)j * 20]); });
+                for (int j = 0; j < k; j++) {
+                    Member &m = mem[(size_t)member[(size_t)j]];
+                    m.alive = false;                                              // until the segment proves clean
+                    if (st[(size_t)j] != ZPQ_OK || first[j] != 0u) continue;      // overflow, store full, PP byte != 0: replayed
+                    // Decoder.skip (decoder.v:151-196) and read_segment_end (decompressor.v:590-635), as in pass 3
+                    size_t p = m.pos + cons[j];
+                    auto get = [&]() -> int { return p < n ? arc[p++] : -1; };
+                    uint32_t curr = code[j];
+                    bool ok = true;
+                    int marker = -1;
+                    if (curr == 0) { const int c = get(); if (c < 0) ok = false; else curr = (uint32_t)c; }
+                    while (ok && curr != 0) { const int c = get(); if (c < 0) { ok = false; break; } curr = (curr << 8) | (uint32_t)c; }
+                    while (ok) { const int c = get(); if (c < 0) break; if (c != 0) { marker = c; break; } }
+                    if (marker == 253) {
+                        if (p + 20 > n || memcmp(arc + p, &sha[(size_t)j * 20], 20) != 0) continue;
+                        p += 20;
+                    } else if (marker != 254) continue;
+                    if (p >= blocks[(size_t)m.bi].next_tag) continue;            // ran out of its block: damage
+                    ArchiveFile f;
+                    f.name = m.name; f.comment = m.comment; f.size = len[j];
+                    if (want_data) f.data.assign(out.data() + out_off[(size_t)j], out.data() + out_off[(size_t)j] + len[j]);
+                    m.files.push_back(std::move(f));
+                    // find_filename for the next segment (decompressor.v:350-429)
+                    const int after = get();
+                    if (after == 0xFF) { m.alive = true; m.finished = true; m.end = p; continue; }
+                    if (after != 1) continue;
+                    m.name.clear(); m.comment.clear();
+                    bool good = true;
+                    for (;;) { const int c = get(); if (c < 0 || c == 0xFF) { good = false; break; } if (c == 0) break; m.name.push_back((char)c); }
+                    for (; good;) { const int c = get(); if (c < 0) { good = false; break; } if (c == 0) break; m.comment.push_back((char)c); }
+                    if (!good || get() < 0 || p >= blocks[(size_t)m.bi].next_tag) continue;
+                    m.pos = p;
+                    m.alive = true;
+                }
+            }
+            for (Member &m : mem) {
+                if (!m.finished || m.files.empty()) continue;
+                Decoded &d = dec[(size_t)m.bi];
+                d.done = true;
+                d.end = m.end;
+                d.f = std::move(m.files[0]);
+                d.more.assign(std::make_move_iterator(m.files.begin() + 1), std::make_move_iterator(m.files.end()));
             }
         }
     }
@@ -784,6 +1101,16 @@ zpqf_archive *zpqf_archive_add_multi(zpq_ctx *const *ctxs, int nctx, int level, 
         if (!ctxs || nctx <= 0) return (int)ZPQ_E_ARG;
         return zpaq::archive_add_views(std::vector<zpq_ctx *>(ctxs, ctxs + nctx), level, nfiles, names, comments, data, lens, &h->bytes,
                                        (size_t)fragment_bytes);
+    });
+}
+zpqf_archive *zpqf_archive_add_solid(zpq_ctx *const *ctxs, int nctx, int level, int nfiles, const char *const *names,
+                                     const char *const *comments, const uint8_t *const *data, const uint64_t *lens,
+                                     uint64_t fragment_bytes, int solid_files, int *rc)
+{
+    return archive_call(rc, __func__, [&](zpqf_archive *h) {
+        if (!ctxs || nctx <= 0) return (int)ZPQ_E_ARG;
+        return zpaq::archive_add_views(std::vector<zpq_ctx *>(ctxs, ctxs + nctx), level, nfiles, names, comments, data, lens, &h->bytes,
+                                       (size_t)fragment_bytes, solid_files);
     });
 }
 zpqf_archive *zpqf_archive_extract_multi(zpq_ctx *const *ctxs, int nctx, const uint8_t *arc, size_t n, int want_data, int *rc)

@@ -116,9 +116,17 @@ struct BitCtx {
 // its byte loop, for the rest of its input; the decoder reports ONCE, there, that the first stripe of its output is
 // stored.  Only these instantiations carry that code: the mere presence of the wait inside the byte loop cost the
 // level-2 encoder 7 % (218 vs 204 ms), more than the overlap gains.
-template <bool DEC, bool SPEC, int NCH, bool MIXT, int GG, bool SP, bool HIO = false>
+// KEEP = state hand-over between launches (block sets: one launch codes ONE segment of each block, compressor.v:238-245,
+// decompressor.v:413-418).  Load: a block starts from the state in its slot instead of Predictor.init -- no slot clear, no
+// init image.  Save: it leaves its complete state there: the LDS tables in the components' cm areas (ICM cm[256], ISSE weight
+// pairs, as the lane-0 kernel keeps them), the last nibble's rows, the MIX2 weights still in registers / LDS, the VM state
+// (DVmRegs: the interpreter's registers, or prev / m4, b4 in its pad words), the line store's claim count and full flag
+// (DCompScal a / b of the component, which only a MATCH uses otherwise).  Block i works on slot slot_map[i], one block per
+// slot and launch.  The byte loop is the same code: everything KEEP adds sits in front of it and behind it.
+template <bool DEC, bool SPEC, int NCH, bool MIXT, int GG, bool SP, bool HIO = false, bool KEEP = false>
 __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg cfg)
 {
+    static_assert(!(KEEP && HIO), "block sets take no part in striped transfers");
     constexpr int G = GG;            // shadows zpqc::G inside the kernel
     constexpr int BPW = 64 / GG;
     extern __shared__ __align__(16) u8 lds[];
@@ -176,6 +184,11 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
     const int slot_id = blockIdx.x * cfg.blocks_per_wg + bslot;
     const int nslots = B.nslots;                       // may be less than gridDim.x * blocks_per_wg
     u8 *slot = B.slots + (u64)slot_id * M.slot_bytes;
+    if constexpr (KEEP) {
+        // (groups beyond the batch code nothing; they only must not read past the map)
+        const int si = slot_id < nslots ? slot_id : 0;
+        slot = B.slots + (u64)(B.slot_map ? B.slot_map[si] : si) * M.slot_bytes;
+    }
     u8 *my = lds + L_STATE + bslot * cfg.lds_per_block;
 
     const int n = NCH ? NCH + (MIXT ? 1 : 0) : cfg.n;
@@ -252,7 +265,29 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
 
     for (int blk = slot_id; slot_id < nslots && blk < B.nblocks; blk += nslots) {
         // ---- Predictor.init + ZPAQL.clear for this block (predictor.v:325-470, zpaql.v:54-95)
-        {
+        if constexpr (KEEP) {
+            // ... or the state an earlier launch left in the slot: counters and weights back into their LDS packing (the ICM's
+            // stretch rebuilt as below); the hash tables, the store's tags, H / M and the MIX2's weights are used where they are
+            for (int c = 0; c < n; c++) {
+                const DComp &cc = M.comp[c];
+                if (cc.type != ZT_ICM && cc.type != ZT_ISSE) continue;
+                u32 *d32 = reinterpret_cast<u32 *>(my + cfg.lds_off32[c]);
+                u8 *d8 = my + cfg.lds_off8[c];
+                const u32 *cmk = reinterpret_cast<const u32 *>(slot + cc.cm_off);
+                for (int i = li; i < 256; i += G) {
+                    if (cc.type == ZT_ICM) {
+                        const u32 cmi = cmk[i] & 0x7FFFFFu;
+                        const i32 sti = stretch_of(cmi);
+                        d32[i] = cmi | (((u32)sti & 0x1FFu) << 23);
+                        d8[i] = (u8)(sti >> 9);
+                    } else {
+                        const u32 a0 = cmk[2 * i], a1 = cmk[2 * i + 1];
+                        d32[i] = (a0 & 0xFFFFFu) | (a1 << 20);
+                        d8[i] = (u8)((i32)a1 >> 12);
+                    }
+                }
+            }
+        } else {
             uint4 *z4 = reinterpret_cast<uint4 *>(slot);
             const u64 n16 = M.zero_bytes / 16;
             const uint4 zero = make_uint4(0, 0, 0, 0);
@@ -299,6 +334,11 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
         z.r = reinterpret_cast<u32 *>(slot + M.r_off);
         z.hdr = M.header; z.hdr_len = M.hdr_len; z.hbegin = M.hbegin; z.hend = M.hend;
         u32 prev = 0, m4 = 0, b4 = 0, hctx = 0;
+        DVmRegs *const kregs = reinterpret_cast<DVmRegs *>(slot + M.regs_off);
+        if constexpr (KEEP) {
+            z.a = kregs->a; z.b = kregs->b; z.c = kregs->c; z.d = kregs->d; z.f = kregs->f; z.pc = kregs->pc;
+            prev = kregs->pad_[0]; m4 = kregs->pad_[0]; b4 = kregs->pad_[1];
+        }
 
         // Input window: the next bytes of `src` live in two registers, refilled by aligned
         // dword loads issued a whole dword ahead of use (never a load on the bit path).
@@ -455,6 +495,10 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
         u32x4 n_tags = {0, 0, 0, 0};
         bool sp_full = false;
         u32 sp_claims = 0;
+        DCompScal *const kscal = reinterpret_cast<DCompScal *>(slot + M.scal_off) + (lc < n ? lc : 0);
+        if constexpr (KEEP && SP) {
+            if (hashed) { sp_claims = (u32)kscal->a; sp_full = kscal->b != 0; }
+        }
         const u32 sp_limit = sp_cap - (sp_cap >> 4);       // a block that needs more than 15/16 of the store is refused
         // second request of the non-HYP decoders (see TWO below): the rows for the other outcome of the nibble's last bit
         u32x4 aA = {0, 0, 0, 0}, aB = {0, 0, 0, 0}, aC = {0, 0, 0, 0}, a_tags = {0, 0, 0, 0};
@@ -504,7 +548,7 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
 #ifdef ZPQ_NO_SWZ
         constexpr bool SWZ = false;
 #else
-        constexpr bool SWZ = HYP;
+        constexpr bool SWZ = HYP && !KEEP;             // (a kept table outlives the launch: every kernel must find it in the reference's layout)
 #endif
         const u32 swz_q = hashed && C.ht_len >= 1024u ? (u32)(31 - __clz((int)C.ht_len)) - 8u : 0u;   // log2(quarter) - 6; 0 = table too small
         auto swz_addr = [&](const u32 h0) -> u32 {
@@ -718,8 +762,10 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
         const bool mixreg = NCH ? MIXT : (has_mix2 && (mix_mask & 255u) == 255u && mix_cmask >= 255u);
         u32 mw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         u32 mh_prev = 0, mch_prev = 0;
+        // (KEEP: the ICM's cm area holds state, and the workgroup's first slot may be anybody's: the lane's own pad word)
         u16 *const ax16 = (ctype == ZT_MIX2) ? a16
-                                             : reinterpret_cast<u16 *>(B.slots + (u64)(blockIdx.x * cfg.blocks_per_wg) * M.slot_bytes + M.comp[0].cm_off);
+                          : KEEP ? reinterpret_cast<u16 *>(&kscal->pad_[0])
+                                 : reinterpret_cast<u16 *>(B.slots + (u64)(blockIdx.x * cfg.blocks_per_wg) * M.slot_bytes + M.comp[0].cm_off);
         const u32 axmask = (ctype == ZT_MIX2) ? mix_cmask : 0u;
         auto mix_byte_begin = [&](const u32 byte, const bool have_prev) {
             if (have_prev) {
@@ -1387,6 +1433,53 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
 
         if (DEC && pend_store) dst[pend_pos] = (u8)pend_val;
         // (the last nibble's row is not written back: the slot is re-initialised for the next block)
+        if constexpr (KEEP) {
+            // ---- ... unless the block goes on in a later launch: everything that lives in registers and LDS into the slot.
+            // Two hypotheses: both copies hold the same row, hash and bookkeeping after the take-over; copy 0 saves.
+            const bool any_byte = DEC ? (X.opos != 0u || got_first) : (total != 0u);
+            if (any_byte && wr_lane) *reinterpret_cast<u32x4 *>(tbase + roff) = u32x4{X.r0, X.r1, X.r2, X.r3};
+            if (!DEC && mixreg && mix_lane && any_byte) {
+                // encoder: the last byte's eight weights (mix_byte_begin writes them when the NEXT byte begins)
+#pragma unroll
+                for (int t = 0; t < 8; t++) ax16[(mh_prev + ((1u << t) | (mch_prev >> (8 - t)))) & axmask] = (u16)mw[t];
+            }
+            if constexpr (DEC && MIXS) {
+                // two-hypothesis decoder: the ended nibble's candidates (mixs_arrive writes them when the next nibble's arrive)
+#pragma unroll
+                for (int q = 0; q < 2; q++) {
+                    const u32 sl = (u32)(li >> 1) + 8u * (u32)q;
+                    if (mix_live && hyp == 0 && sl >= 1u) a16m[ms_cur[q]] = w16s[sl];
+                }
+            }
+            // (the one-copy decoders wrote theirs back in the last bit step, mixw_request; the runtime path trains in the slot)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            for (int c = 0; c < n; c++) {
+                const DComp &cc = M.comp[c];
+                if (cc.type != ZT_ICM && cc.type != ZT_ISSE) continue;
+                const u32 *d32 = reinterpret_cast<const u32 *>(my + cfg.lds_off32[c]);
+                const u8 *d8 = my + cfg.lds_off8[c];
+                u32 *cmk = reinterpret_cast<u32 *>(slot + cc.cm_off);
+                for (int i = li; i < 256; i += G) {
+                    const u32 v = d32[i];
+                    if (cc.type == ZT_ICM) cmk[i] = v & 0x7FFFFFu;
+                    else {
+                        cmk[2 * i] = (u32)(((i32)(v << 12)) >> 12);
+                        cmk[2 * i + 1] = ((u32)(i32)(int8_t)d8[i] << 12) | (v >> 20);
+                    }
+                }
+            }
+            if (li == 0) {
+                const int vm_kind = NCH == 0 ? cfg.vm_kind : (NCH == 2 ? (int)VM_LEVEL1 : (int)VM_HASHCHAIN);
+                kregs->a = z.a; kregs->b = z.b; kregs->c = z.c; kregs->d = z.d; kregs->f = z.f; kregs->pc = z.pc;
+                kregs->pad_[0] = vm_kind == VM_LEVEL1 ? m4 : prev;
+                kregs->pad_[1] = b4;
+            }
+            if constexpr (SP) {
+                if (wr_lane) { kscal->a = (i32)sp_claims; kscal->b = sp_full ? 1 : 0; }
+            }
+        }
         // ---- segment end: compress(-1) + flush (encoder.v:101-105,130-139)
         if (!DEC && is_last) {
             X.high = X.low;                                   // encode(1, 0): mid = low, high = mid
@@ -1584,10 +1677,14 @@ extern "C" int zpq_launch_chain(const DBatch *B, const DModel *hostM, int decode
     if (hyp16) cfg.g = 16;
     if (blocks_per_wg < 64 / cfg.g || blocks_per_wg > cfg.blocks_per_wg || blocks_per_wg % (64 / cfg.g)) return ZPQ_E_INTERNAL;
     if (name_out) *name_out = decode ? "k_chain<decode>" : "k_chain<encode>";
-    if (!decode && zpq_pipe_applies(hostM, blocks_per_wg, B->nslots)) {
+    // a block set's launch (state hand-over through the slots): k_chain<..., KEEP> in both directions, whatever the batch
+    // planner would pick for independent blocks -- the pipe kernels keep no state
+    const bool keep = (B->flags & ZB_KEEP_STATE) != 0;
+    if (keep && (hio || B->nslots < B->nblocks)) return ZPQ_E_INTERNAL;   // one block per slot and launch
+    if (!keep && !decode && zpq_pipe_applies(hostM, blocks_per_wg, B->nslots)) {
         return zpq_launch_pipe(B, hostM, nwg, blocks_per_wg, stream, name_out);   // "k_pipe<encode>" or "k_pipe2<encode>" (split stages)
     }
-    if (decode && !B->prog_counter && zpq_dpipe_applies(hostM, blocks_per_wg, B->nslots)) {
+    if (!keep && decode && !B->prog_counter && zpq_dpipe_applies(hostM, blocks_per_wg, B->nslots)) {
         if (name_out) *name_out = "k_dpipe<decode>";
         return zpq_launch_dpipe(B, hostM, nwg, blocks_per_wg, stream);
     }
@@ -1603,11 +1700,15 @@ extern "C" int zpq_launch_chain(const DBatch *B, const DModel *hostM, int decode
                        (size_t)cfg.blocks_per_wg * cfg.lds_per_block + 1280;
     if (lds > 160 * 1024) return ZPQ_E_INTERNAL;
     // encode uses the pipelined bit step, decode the plain one (measured, see above)
-#define ZPQ_LAUNCH(D, N, MX, GGv, SPv)                                                                   \
+#define ZPQ_LAUNCH_K(D, N, MX, GGv, SPv, KP)                                                             \
     do {                                                                                                 \
         constexpr bool S_ = (D) ? CHAIN_SPEC_DEC : CHAIN_SPEC_ENC;                                       \
-        (void)hipFuncSetAttribute((const void *)zpqc::k_chain<D, S_, N, MX, GGv, SPv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        hipLaunchKernelGGL((zpqc::k_chain<D, S_, N, MX, GGv, SPv>), dim3(nwg), dim3(threads), lds, stream, *B, cfg); \
+        (void)hipFuncSetAttribute((const void *)zpqc::k_chain<D, S_, N, MX, GGv, SPv, false, KP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+        hipLaunchKernelGGL((zpqc::k_chain<D, S_, N, MX, GGv, SPv, false, KP>), dim3(nwg), dim3(threads), lds, stream, *B, cfg); \
+    } while (0)
+#define ZPQ_LAUNCH(D, N, MX, GGv, SPv)                                                                   \
+    do {                                                                                                 \
+        if (keep) ZPQ_LAUNCH_K(D, N, MX, GGv, SPv, true); else ZPQ_LAUNCH_K(D, N, MX, GGv, SPv, false);  \
     } while (0)
 #define ZPQ_LAUNCH_HIO(D, N)                                                                             \
     do {                                                                                                 \
@@ -1639,5 +1740,6 @@ extern "C" int zpq_launch_chain(const DBatch *B, const DModel *hostM, int decode
 #undef ZPQ_LAUNCH_SP
 #undef ZPQ_LAUNCH_HIO
 #undef ZPQ_LAUNCH
+#undef ZPQ_LAUNCH_K
     return ZPQ_OK;
 }

@@ -75,7 +75,13 @@ struct DBatch {
     uint32_t *final_code;        // decode only (may be null)
     uint32_t *first_byte;        // decode only (may be null)
     int32_t *status;
-    int32_t *trace;              // predict() per modelled bit of block 0 (may be null)
+    union {
+        int32_t *trace;          // predict() per modelled bit of block 0 (may be null; the lane-0 kernel only)
+        // Block sets (k_chain<..., KEEP>, launches with ZB_KEEP_STATE only): block i works on slot slot_map[i] and each slot
+        // codes one block per launch; null = block i on slot i.  (It shares the trace pointer's place, which no chain kernel
+        // reads, so that the kernels' argument block -- and with it the existing instantiations' code -- stays as it was.)
+        const int32_t *slot_map;
+    };
     uint32_t *ctx_out;           // debug: H[0..n) per byte of block 0 (may be null)
     // read-only tables in HBM (L2-resident)
     const int16_t *squash;       // [4096]   predictor.v:21-49 (entry 4095 unused)

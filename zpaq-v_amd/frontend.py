@@ -45,6 +45,8 @@ def _lib():
     L.zpqf_archive_add.restype = vp
     L.zpqf_archive_add.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.zpqf_archive_add_fragmented.restype = vp
+    L.zpqf_archive_add_solid.restype = vp
+    L.zpqf_archive_add_solid.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_uint64, C.c_int, vp]
     L.zpqf_archive_add_fragmented.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_uint64, vp]
     L.zpqf_archive_add_multi.restype = vp
     L.zpqf_archive_add_multi.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_uint64, vp]
@@ -189,10 +191,11 @@ class Decompresser:
         return out.raw
 
 
-def archive_add(ctx, level, files, fragment_bytes=0):
+def archive_add(ctx, level, files, fragment_bytes=0, solid=0):
     """zpaq::archive_add: the reference CLI's add loop (cmd/main.v:283-311) for a list of
     (name, comment, data) as ONE GPU batch.  Returns the archive bytes.  fragment_bytes > 0 cuts
-    longer files into blocks of that size (continuation blocks carry an empty name)."""
+    longer files into blocks of that size (continuation blocks carry an empty name).  solid = N > 1 puts N
+    consecutive pieces into one block, a segment each (coded as block sets); 0 or 1 = one block per piece."""
     L = _lib()
     n = len(files)
     names = (C.c_char_p * n)(*[f[0].encode() for f in files])
@@ -201,7 +204,11 @@ def archive_add(ctx, level, files, fragment_bytes=0):
     data = (C.c_char_p * n)(*keep)
     lens = (C.c_uint64 * n)(*[len(k) for k in keep])
     rc = C.c_int(0)
-    if isinstance(ctx, (list, tuple)):                       # several GPUs: block b -> ctx[b mod G]
+    if solid > 1:
+        ctxs = list(ctx) if isinstance(ctx, (list, tuple)) else [ctx]
+        arr = (C.c_void_p * len(ctxs))(*[c.h if c is not None else None for c in ctxs])
+        h = L.zpqf_archive_add_solid(arr, len(ctxs), level, n, names, comments, data, lens, fragment_bytes, solid, C.byref(rc))
+    elif isinstance(ctx, (list, tuple)):                     # several GPUs: block b -> ctx[b mod G]
         arr = (C.c_void_p * len(ctx))(*[c.h for c in ctx])
         h = L.zpqf_archive_add_multi(arr, len(ctx), level, n, names, comments, data, lens, fragment_bytes, C.byref(rc))
     else:
