@@ -90,6 +90,14 @@ int zpq_ctx_set_state_budget(zpq_ctx *, uint64_t bytes);
 int zpq_ctx_set_max_block_bytes(zpq_ctx *, uint64_t bytes);
 /* Resident blocks (state slots) the last batch call used; for reporting. */
 int zpq_ctx_last_slots(const zpq_ctx *);
+/* What the host pipeline did with the last host-pointer batch call (zpq_encode_blocks / zpq_decode_blocks of two or
+ * more blocks): bit 0 = the input was uploaded in two stripes, the second one beside the running encoder; bit 1 = the
+ * first stripe of the output was copied out beside the running decoder; bits 8 and up = the number of rounds.
+ * 0 for a NULL or closed ctx, before any call, and after a batch call that did not go through that pipeline (a _dev
+ * call, a single block or segment, a call that failed or was refused for its arguments).  Calls that code nothing
+ * (zpq_gather_dev, zpq_sha1_*) leave it as it is.  For reporting and for tests that must know which transfer path
+ * they exercised. */
+unsigned zpq_ctx_last_host_transfer(const zpq_ctx *);
 /* Capacity (64-byte lines per hash table) of the compact line store the last batch call's kernel ran with;
  * 0 = dense tables.  For reporting and for tests that must know which instantiation they exercised. */
 unsigned zpq_ctx_last_line_store(const zpq_ctx *);
@@ -140,6 +148,11 @@ int zpq_decode_blocks(zpq_ctx *, const zpq_model *, int nblocks, const uint8_t *
  * zpq_host_alloc (pinned, device-visible) make the transfers plain DMA and let the GPU pack each block's
  * produced bytes straight into the caller's slab -- only bytes that exist cross PCIe.  Pageable buffers
  * work too (staged copies by the runtime, whole slabs come back).  One slab may be at most 4 GiB - 16.
+ * A decoder's batch of 64 or more equal pinned slabs of at least 16 KiB MAY leave in two stripes (it does for a
+ * dense short chain model coded in a single round; bit 1 of zpq_ctx_last_host_transfer says so): the first
+ * E = (3/4 of the slab, rounded down to 256) bytes of EVERY slab are then copied beside the running kernel, whatever
+ * the block produced.  Bytes in [out_len[b], E) of such a slab are unspecified; bytes from max(out_len[b], E) on are
+ * not written.
  */
 void *zpq_host_alloc(size_t bytes);
 void zpq_host_free(void *);

@@ -31,6 +31,14 @@ def test_library_exports_every_declared_symbol(zpq):
         assert hasattr(L, n), "missing export: " + n
 
 
+def test_reporting_calls_take_a_null_context(zpq):
+    """The "what did the last call do" getters answer 0 / "" for a NULL ctx (nothing to report, no crash)."""
+    L = zpq.lib()
+    assert L.zpq_ctx_last_host_transfer(None) == 0
+    assert L.zpq_ctx_last_slots(None) == 0 and L.zpq_ctx_last_line_store(None) == 0
+    assert L.zpq_ctx_last_kernel_name(None) == b""
+
+
 def test_tables_match_oracle(zpq):
     L = zpq.lib()
     sq = (C.c_int32 * 4096)(); st = (C.c_int32 * 32768)()

@@ -85,6 +85,8 @@ def lib():
     L.zpq_ctx_set_state_budget.argtypes = [vp, u64]
     L.zpq_ctx_set_max_block_bytes.argtypes = [vp, u64]
     L.zpq_ctx_last_slots.argtypes = [vp]
+    L.zpq_ctx_last_host_transfer.argtypes = [vp]
+    L.zpq_ctx_last_host_transfer.restype = C.c_uint
     L.zpq_ctx_last_line_store.argtypes = [vp]
     L.zpq_ctx_last_line_store.restype = C.c_uint
     L.zpq_ctx_resident_capacity.argtypes = [vp, vp, u32]
@@ -270,6 +272,12 @@ class Context:
     @property
     def last_slots(self):
         return lib().zpq_ctx_last_slots(self.h)
+
+    @property
+    def last_host_transfer(self):
+        """What the host pipeline did with the last host-pointer batch: bit 0 striped upload, bit 1 early download,
+        bits 8 and up the number of rounds (zpq_ctx_last_host_transfer)."""
+        return lib().zpq_ctx_last_host_transfer(self.h)
 
     @property
     def last_line_store(self):

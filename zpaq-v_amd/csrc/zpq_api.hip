@@ -107,6 +107,7 @@ struct zpq_ctx {
     DevBuf slots;
     uint64_t budget = 0;
     int last_slots = 0;
+    unsigned last_host = 0;                // what host_pipeline did with the last host-pointer batch (zpq_ctx_last_host_transfer)
     uint32_t last_sp = 0;                  // line-store capacity the last launch ran with (0 = dense)
     const char *last_name = "";
     // staging for the host-pointer entry points
@@ -357,6 +358,7 @@ static int set_max_block_bytes(zpq_ctx *c, uint64_t bytes)
     return ZPQ_OK;
 }
 extern "C" int zpq_ctx_last_slots(const zpq_ctx *c) { return ctx_live(c) ? c->last_slots : 0; }
+extern "C" unsigned zpq_ctx_last_host_transfer(const zpq_ctx *c) { return ctx_live(c) ? c->last_host : 0u; }
 extern "C" unsigned zpq_ctx_last_line_store(const zpq_ctx *c) { return ctx_live(c) ? c->last_sp : 0u; }
 extern "C" const char *zpq_ctx_last_kernel_name(const zpq_ctx *c) { return ctx_live(c) ? c->last_name : ""; }
 extern "C" float zpq_ctx_last_kernel_ms(const zpq_ctx *c) try
@@ -542,6 +544,7 @@ static int run_batch(zpq_ctx *c, const zpq_model *m, int decode, const BatchArgs
     B.nslots = nslots;
     c->last_slots = nslots;
     c->last_sp = P.sp;
+    c->last_host = 0;                                            // (host_pipeline sets it when its batch is through)
 
     HIPCK(hipEventRecord(c->ev0, c->stream));
     if (want_chain && !a.own_slot) {
@@ -601,6 +604,8 @@ static int host_batch(zpq_ctx *c, const zpq_model *m, int decode, int nblocks, c
                       uint32_t ntrace, uint32_t *ctx_out, size_t ctx_words)
 {
     if (!ctx_live(c)) return c ? ZPQ_E_CLOSED : ZPQ_E_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->last_host = 0;                                            // (whatever becomes of this call: host_pipeline sets it at its end)
     if (!m || nblocks < 0) return ZPQ_E_ARG;
     if (nblocks == 0) return ZPQ_OK;
     if (!in_off || !out_off || !out_len || !status) return ZPQ_E_ARG;
@@ -610,7 +615,6 @@ static int host_batch(zpq_ctx *c, const zpq_model *m, int decode, int nblocks, c
             return ZPQ_E_ARG;
     const size_t in_bytes = (size_t)in_off[nblocks], out_bytes = (size_t)out_off[nblocks];
     if ((in_bytes && !in) || (out_bytes && !out)) return ZPQ_E_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
     HIPCK(hipSetDevice(c->device));
     if (nblocks >= 2 && !own_slot && !trace && !ctx_out)
         return host_pipeline(c, m, decode, nblocks, in, in_off, flags, out, out_off, out_len, consumed, final_code, first_byte, status);
@@ -699,6 +703,7 @@ static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, int nblocks
                          uint32_t *final_code, uint32_t *first_byte, int32_t *status)
 {
     HIPCK(hipSetDevice(c->device));
+    c->last_host = 0;
     Plan P0;
     int rc = plan_batch(c, m, flags, nblocks, false, false, &P0, decode);
     if (rc != ZPQ_OK) return rc;
@@ -727,6 +732,12 @@ static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, int nblocks
     c->pipe[0].n = c->pipe[1].n = 0;
     const uint32_t *gate_flag_dev = nullptr;
     uint64_t stripe_L = 0, early_L = 0;
+    unsigned did = 0;                                                           // bit 0: striped upload, bit 1: early download
+    uint32_t stripe_delay_us = 0;
+    if (const char *ev = getenv("ZPQ_STRIPE_DELAY_US")) {                       // tests: lanes reach the gate before the second stripe is sent
+        const unsigned long long v = strtoull(ev, nullptr, 0);
+        stripe_delay_us = v > 500000ull ? 500000u : (uint32_t)v;
+    }
     for (int r = 0; r < nrounds; r++) {
         zpq_ctx::PipeSet &S = c->pipe[r & 1];
         const int b0 = r * per_round, b1 = (b0 + per_round < nblocks) ? b0 + per_round : nblocks, n = b1 - b0;
@@ -801,6 +812,10 @@ static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, int nblocks
         if (striped) {
             // the rest of every block, beside the running kernel; then the signal (whatever happened: a kernel left
             // waiting for it would only end at its spin limit)
+            if (rc == ZPQ_OK && stripe_delay_us) {
+                struct timespec ts = {(time_t)(stripe_delay_us / 1000000u), (long)(stripe_delay_us % 1000000u) * 1000L};
+                nanosleep(&ts, nullptr);
+            }
             hipError_t e2 = rc == ZPQ_OK ? hipMemcpy2DAsync((uint8_t *)S.in.p + stripe, stripe_L, in + in_base + stripe, stripe_L, stripe_L - stripe,
                                                             (size_t)n, hipMemcpyHostToDevice, c->s_h2d) : hipSuccess;
             if (e2 == hipSuccess) e2 = hipStreamSynchronize(c->s_h2d);
@@ -808,6 +823,7 @@ static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, int nblocks
             if (e2 != hipSuccess && rc == ZPQ_OK) { (void)hipDeviceSynchronize(); return ZPQ_E_NODEVICE; }
         }
         if (rc != ZPQ_OK) { (void)hipDeviceSynchronize(); return rc; }
+        if (striped) did |= 1u;
         HIPCK(hipEventRecord(S.ev_k, c->stream));
         uint32_t skip = 0;
         if (prog_dev) {
@@ -820,6 +836,7 @@ static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, int nblocks
                 struct timespec ts = {0, 50000};
                 nanosleep(&ts, nullptr);
             }
+            if (skip) did |= 2u;
             if (skip) HIPCK(hipMemcpy2DAsync(out + out_base, early_L, S.out.p, early_L, skip, (size_t)n, hipMemcpyDeviceToHost, c->s_d2h));
         }
         // ---- download on the copy-out stream
@@ -845,6 +862,7 @@ static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, int nblocks
     HIPCK(hipStreamSynchronize(c->stream));
     deliver(c->pipe[nrounds & 1]);                                             // (older round first)
     deliver(c->pipe[(nrounds + 1) & 1]);
+    c->last_host = did | ((unsigned)nrounds << 8);
     return ZPQ_OK;
 }
 
