@@ -136,6 +136,14 @@ int zpq_encode_blocks(zpq_ctx *, const zpq_model *, int nblocks, const uint8_t *
  * Decoder.skip() (decoder.v:151-196) from there; final_code[b] = Decoder.code at
  * EOF (skip() starts from it); first_byte[b] = the PP byte when ZPQ_FLAG_PP
  * (else 0xFFFFFFFF).  consumed/final_code/first_byte may be NULL.
+ * The input window may be longer than the stream (junk behind it: consumed stays at the stream's end) or shorter (a
+ * stream without its tail): bytes at or past in_off[b+1] read as 0, the way the reference's Decoder shifts in nothing
+ * when its Reader returns -1 (decoder.v:57-62), whatever lies behind the block in `in`.
+ * A slab too small: with cap = out_off[b+1] - out_off[b], a decoder stops right after it has decoded byte cap + 1 (the
+ * PP byte of ZPQ_FLAG_PP not counted); out_len[b] is then cap + 1 and status[b] ZPQ_E_OVERFLOW, consumed[b] and
+ * final_code[b] are those of that point, and the cap bytes in the slab are the decoded prefix.  A stream that ends with
+ * byte cap is ZPQ_OK.  The encoders keep counting instead: out_len[b] is the full coded length, the slab holds its first
+ * cap bytes.  The device-pointer forms write no byte from min(out_len[b], cap) on, in either direction.
  */
 int zpq_decode_blocks(zpq_ctx *, const zpq_model *, int nblocks, const uint8_t *in,
                       const uint64_t *in_off, uint32_t flags, uint8_t *out,

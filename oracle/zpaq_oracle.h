@@ -119,6 +119,16 @@ int64_t zo_decode_segment(zo_codec *, const uint8_t *in, size_t n, uint8_t *out,
                           size_t *consumed, zo_trace_bit *trace, size_t ntrace);
 
 /*
+ * The same decode, stopped where the GPU decoders stop: a byte is stored while fewer than `cap` have been
+ * decoded, and decoding ends at a decoded EOF or right after byte number cap + 1 (no further bit is pulled),
+ * whichever is first.  *out_len = bytes decoded (cap + 1 on overflow), *consumed and *final_code = the
+ * Reader position and Decoder.code at that point, *vm_overflow = 1 if HCOMP hit the step cap in this
+ * segment.  The PP byte is byte 0 like any other.  Returns 0, or -1 on overflow.
+ */
+int zo_decode_prefix(zo_codec *, const uint8_t *in, size_t n, uint8_t *out, size_t cap,
+                     size_t *out_len, size_t *consumed, uint32_t *final_code, int *vm_overflow);
+
+/*
  * Batch helpers (fresh model per block, one segment per block) used as the
  * CPU baseline and for bulk parity checks.  Block b reads
  * in[in_off[b]..in_off[b+1]) and writes out[out_off[b]..out_off[b+1]);

@@ -66,6 +66,7 @@ def lib():
     L.zo_encode_segment.argtypes = [vp, u8p, sz, C.c_uint, vp, sz, vp, sz]
     L.zo_decode_segment.restype = i64
     L.zo_decode_segment.argtypes = [vp, u8p, sz, vp, sz, vp, vp, sz]
+    L.zo_decode_prefix.argtypes = [vp, u8p, sz, vp, sz, vp, vp, vp, vp]
     L.zo_encode_blocks.argtypes = [u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint, vp, vp, vp, C.c_int]
     L.zo_decode_blocks.argtypes = [u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int]
     L.zo_sha1.argtypes = [u8p, sz, vp]
@@ -124,6 +125,15 @@ class Codec:
         if n < 0:
             raise OverflowError("oracle decode overflow")
         return out.raw[:n], cons.value
+
+    def decode_prefix(self, coded, cap):
+        """Decode with the GPU decoders' stop rule (zo_decode_prefix): EOF, or right after byte cap + 1.
+        Returns (stored bytes, out_len, consumed, final_code, vm_overflow); out_len == cap + 1 on overflow."""
+        out = C.create_string_buffer(max(cap, 1))
+        olen, cons, code, vmo = C.c_size_t(), C.c_size_t(), C.c_uint32(), C.c_int()
+        lib().zo_decode_prefix(self.h, coded, len(coded), out, cap, C.byref(olen), C.byref(cons), C.byref(code),
+                               C.byref(vmo))
+        return out.raw[:min(olen.value, cap)], olen.value, cons.value, code.value, bool(vmo.value)
 
 
 def encode_blocks(header, blocks, pp=True, nthreads=1, slack=None):

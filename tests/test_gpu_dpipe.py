@@ -19,7 +19,8 @@ pytestmark = pytest.mark.gpu
 
 
 def decode_both(zpq, gpu_ctx, monkeypatch, model, coded, cap, flags=None):
-    """Decode with both decoders; everything the ABI returns must agree (a refused block's bytes are unspecified)."""
+    """Decode with both decoders; everything the ABI returns must agree (a refused block's bytes are the decoded prefix:
+    test_gpu_offnominal.py holds them to the oracle)."""
     kw = {} if flags is None else {"flags": flags}
     assert len(coded) >= 12                      # (smaller batches stay with the lane-per-component decoder)
     monkeypatch.setenv("ZPQ_DEC_PIPE", "1")      # (opt-in: the lane-per-component decoder measured faster, EXPERIMENTS.md 4.5)
@@ -91,7 +92,8 @@ def test_rounds_and_partial_workgroups(zpq, gpu_ctx, monkeypatch, level):
 
 
 def test_output_overflow_and_garbage_input(zpq, gpu_ctx, monkeypatch):
-    """A slab that is too small is a per-block status (and no byte lands beyond it); random bytes in place of a coded
+    """A slab that is too small is a per-block status (that no byte lands beyond it is checked on
+    sentinel-filled slabs in test_gpu_offnominal.py); random bytes in place of a coded
     stream end with a status or at the slab's end -- both decoders alike, nothing hangs."""
     model = zpq.Model(level=2)
     rnd = random.Random(5)

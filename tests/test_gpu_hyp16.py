@@ -24,7 +24,7 @@ LEVELS = [3, 4]
 
 def decode_both(zpq, gpu_ctx, monkeypatch, model, coded, cap, flags=None):
     """Decode with the sixteen-lane and with the eight-lane decoder; everything the ABI returns must agree (a refused
-    block's bytes are unspecified)."""
+    block's bytes are the decoded prefix: test_gpu_offnominal.py holds them to the oracle)."""
     kw = {} if flags is None else {"flags": flags}
     monkeypatch.delenv("ZPQ_DEC_HYP16", raising=False)
     a = gpu_ctx.decode_blocks(model, coded, cap=cap, **kw)
