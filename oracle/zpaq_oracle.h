@@ -66,6 +66,12 @@ uint32_t zo_vm_m(const zo_vm *, uint32_t i);       /* masked m_get, zpaql.v:178-
 uint32_t zo_vm_r(const zo_vm *, int i);
 int zo_vm_hlen(const zo_vm *);
 int zo_vm_mlen(const zo_vm *);
+uint32_t zo_vm_steps(const zo_vm *);               /* instructions the last run executed (a HALT or an undefined opcode
+                                                      ends a run without counting) */
+int zo_vm_overflow(const zo_vm *);                 /* 1 once any run stopped at the step cap */
+uint32_t zo_vm_step_cap(void);
+/* all of H (hlen words), M (mlen bytes) and R (256 words) in one call; a null pointer skips that part */
+void zo_vm_dump(const zo_vm *, uint32_t *h, uint8_t *m, uint32_t *r);
 
 /* ---- one ZPAQ block's model state: ZPAQL + Predictor
  *      (compressor.v:147-148,184-185; predictor.v:292-470) ---- */

@@ -44,6 +44,11 @@ def lib():
     L.zo_vm_r.argtypes = [vp, C.c_int]
     L.zo_vm_hlen.argtypes = [vp]
     L.zo_vm_mlen.argtypes = [vp]
+    L.zo_vm_steps.restype = C.c_uint32
+    L.zo_vm_steps.argtypes = [vp]
+    L.zo_vm_overflow.argtypes = [vp]
+    L.zo_vm_step_cap.restype = C.c_uint32
+    L.zo_vm_dump.argtypes = [vp, vp, vp, vp]
     L.zo_codec_new.restype = vp
     L.zo_codec_new.argtypes = [u8p, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.zo_codec_new_level.restype = vp

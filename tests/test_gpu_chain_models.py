@@ -78,9 +78,9 @@ def dec_names(rt, ctx, env):
 class Run:
     """One model on the session context: encode / decode helpers that check everything a call returns."""
 
-    def __init__(self, zpq, ctx, mp, hdr):
+    def __init__(self, zpq, ctx, mp, hdr, offs=None):
         self.zpq, self.ctx, self.mp, self.hdr = zpq, ctx, mp, hdr
-        self.model = zpq.Model(header=hdr)
+        self.model = zpq.Model(header=hdr, offsets=offs)         # (offs: stated (cend, hbegin, hend); None = scanned)
         assert self.model.has_fast_path
         self.rt = CM.route(zpq, self.model)
         self.seen = set()

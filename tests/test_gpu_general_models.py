@@ -37,11 +37,11 @@ class Run:
     """One model on the session context: encode / decode helpers that check everything a call returns and the kernel that
     ran.  rt is the route with no knob set: (gpipe, gdec, lanes, k_rows | k_lanes)."""
 
-    def __init__(self, zpq, ctx, mp, hdr):
+    def __init__(self, zpq, ctx, mp, hdr, offs=None):
         self.zpq, self.ctx, self.mp, self.hdr = zpq, ctx, mp, hdr
         for k in KNOBS:
             mp.delenv(k, raising=False)
-        self.model = zpq.Model(header=hdr)
+        self.model = zpq.Model(header=hdr, offsets=offs)         # (offs: stated (cend, hbegin, hend); None = scanned)
         self.rt = GM.route(zpq, self.model)
         self.rows = self.rt[3] == GM.ROWS
         self.seen = set()
