@@ -51,6 +51,20 @@ extern "C" {
 #define ZPQ_FLAG_LANES 8u     /* force the lane-per-component kernel (any model with <= 64 components) */
 #define ZPQ_FLAG_NOEOF 4u     /* encode: stop after the last data byte, no compress(-1)/flush().  Only the
                                  reference's component-less end_segment path needs it (compressor.v:364). */
+#define ZPQ_FLAG_VMPIPE 16u   /* a request: code a general model whose HCOMP program is NOT the shipped hash chain on the
+                                 wave-per-component kernels with an interpreter wave (k_vpipe / k_vdec) instead of
+                                 k_rows.  Honoured when no chain kernel takes the model, neither ZPQ_FLAG_GENERIC nor
+                                 ZPQ_FLAG_NOEOF is set and the model is in those kernels' envelope (the nine component
+                                 types, inputs earlier than their consumer, a MIX of 1-8 inputs, at most 14
+                                 components, rings and header within the LDS); otherwise the call runs exactly as
+                                 without it.  The coded bytes are the same either way; zpq_ctx_last_kernel_name tells
+                                 which kernel ran ("k_vpipe<encode>" / "k_vdec<decode>").  All batch entry points
+                                 (host, _dev, _multi) honour it, and zpq_ctx_resident_capacity answers for the pair
+                                 it selects.  zpq_block_* and zpq_blockset_* ignore both the flag and the variable: a
+                                 block's first segment runs on the batch kernel it ran on before (k_rows for such a
+                                 model), later segments and block sets on k_generic.  The environment decides first:
+                                 ZPQ_VM_PIPE=1 sets it for every call, ZPQ_VM_PIPE=0 clears it (a value that starts
+                                 with neither digit decides nothing). */
 
 /* ---- header helpers: levels.v:26-375 (get_compression_level) and the scan
  *      that defines cend/hbegin/hend, compressor.v:96-145 ---- */

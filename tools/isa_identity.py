@@ -2,7 +2,9 @@
 (llvm-objdump, no GPU needed) and compares, per kernel symbol, the list of instructions with their operands.
     python tools/isa_identity.py OLD.so NEW.so [name filter ...]      (default filters: k_chain k_pipe)
 A k_chain symbol of OLD that NEW lacks is looked up with one more `false` template argument (a parameter added at the end
-with a default).  Prints the kernels that differ with their per-opcode count changes, then the totals."""
+with a default).  What follows a kernel's last s_endpgm is no code -- s_nop fill up to the next symbol's alignment, the
+prefetch guard behind the module's last function, objdump's `...` for a run of it -- and depends on which function comes
+next, so it is left out of the comparison.  Prints the kernels that differ with their per-opcode count changes, then the totals."""
 import collections
 import os
 import re
@@ -42,6 +44,10 @@ def disassemble(so):
                         funcs[cur] = []
                     elif cur and "\t" in ln:
                         funcs[cur].append(re.sub(r"^\s*[0-9a-f]+:\s*", "", ln.split("//")[0]).strip())
+    for name, ins in funcs.items():
+        ends = [i for i, x in enumerate(ins) if x.split()[0] == "s_endpgm"]
+        if ends and all(x.split()[0] in ("s_nop", "s_code_end", "...") for x in ins[ends[-1] + 1:]):
+            del ins[ends[-1] + 1:]
     return funcs
 
 

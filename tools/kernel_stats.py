@@ -40,3 +40,7 @@ if __name__ == "__main__":
     t = kernel_table(sys.argv[1] if len(sys.argv) > 1 else None)
     for k in sorted(t):
         print("%-100s %s" % (k[:100], t[k]))
+    new = []                                             # the pipelines with an interpreter wave: up to 16 waves of one workgroup (vgpr <= 128)
+    for label, key in (("k_vpipe<batched>", "k_vpipeILb1"), ("k_vpipe<bit-serial>", "k_vpipeILb0"), ("k_vdec", "k_vdec")):
+        new += ["%s vgpr %d sgpr %d scratch %d" % (label, t[k]["vgpr"], t[k]["sgpr"], t[k]["scratch"]) for k in sorted(t) if key in k]
+    print("interpreter-wave pipelines: " + "; ".join(new))

@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 FLAG_PP = 1
 FLAG_GENERIC = 2
 FLAG_LANES = 8
+FLAG_VMPIPE = 16
 _LIB = None
 # Handle lifetime on the Python side (the C side tolerates any destroy order as well, include/zpaq_hip.h): every live
 # Context, Block and PinnedArray is tracked; Context.close() closes its blocks first; at interpreter exit everything

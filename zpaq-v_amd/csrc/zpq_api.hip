@@ -42,6 +42,13 @@ extern "C" int zpq_launch_gpipe(const DBatch *B, const DModel *hostM, int nslots
 extern "C" int zpq_gdec_applies(const DModel *M);               // ... and their DECODER, bit-synchronous, a barrier per level of the prediction chain
 extern "C" int zpq_gdec_blocks_per_cu(const DModel *M);
 extern "C" int zpq_launch_gdec(const DBatch *B, const DModel *hostM, int nslots, hipStream_t stream);
+// ... and the same pair with an interpreter wave, for any other HCOMP program (on request: ZPQ_FLAG_VMPIPE / ZPQ_VM_PIPE)
+extern "C" int zpq_vpipe_applies(const DModel *M);
+extern "C" int zpq_vpipe_blocks_per_cu(const DModel *M);
+extern "C" int zpq_launch_vpipe(const DBatch *B, const DModel *hostM, int nslots, hipStream_t stream);
+extern "C" int zpq_vdec_applies(const DModel *M);
+extern "C" int zpq_vdec_blocks_per_cu(const DModel *M);
+extern "C" int zpq_launch_vdec(const DBatch *B, const DModel *hostM, int nslots, hipStream_t stream);
 extern "C" int zpq_chain_blocks_per_wg(const DModel *M);   // 0 = model not supported by the chain kernel
 extern "C" int zpq_chain_max_wgs(const DModel *M, int cus);
 extern "C" int zpq_chain_plan(const DModel *M, int nblocks, int cus, int *blocks_per_wg);
@@ -407,6 +414,7 @@ struct Plan {
     bool chain = false, lanes = false;
     bool gpipe = false;          // lanes family, encode: the wave-per-component pipeline (zpq_gpipe.hip)
     bool gdec = false;           // lanes family, decode: the wave-per-component decoder (zpq_gpipe.hip, k_gdec)
+    bool vpipe = false, vdec = false;   // the same pair with an interpreter wave (k_vpipe / k_vdec), when asked for
     uint32_t sp = 0;             // compact line store capacity (lines), 0 = dense tables
     const DModel *M = nullptr;   // layout the kernels see (dense or compact)
     int nslots = 0, grid = 0, bpw = 0;
@@ -479,7 +487,14 @@ static int plan_batch(zpq_ctx *c, const zpq_model *m, uint32_t flags, int nblock
         nslots = nblocks;
         P->gpipe = P->lanes && !decode && zpq_gpipe_applies(&M) != 0;
         P->gdec = P->lanes && decode && zpq_gdec_applies(&M) != 0;
-        const int cap_res = c->cus * (P->gpipe ? zpq_gpipe_blocks_per_cu(&M) : P->gdec ? zpq_gdec_blocks_per_cu(&M) : P->lanes ? zpq_lanes_blocks_per_cu(&M) : zpq_generic_blocks_per_cu(&M));
+        // ZPQ_FLAG_VMPIPE, a request: ZPQ_VM_PIPE=1 sets it for every call of the process, ZPQ_VM_PIPE=0 clears it
+        // (anything but a leading '0' or '1' decides nothing; a zpq_block's first segment keeps its kernel: ZB_NO_VMPIPE)
+        const char *vev = getenv("ZPQ_VM_PIPE");
+        const bool vm_env = vev && (vev[0] == '0' || vev[0] == '1');
+        const bool vm_pipe = !(flags & ZB_NO_VMPIPE) && (vm_env ? vev[0] == '1' : (flags & ZPQ_FLAG_VMPIPE) != 0);
+        P->vpipe = vm_pipe && P->lanes && !decode && !P->gpipe && zpq_vpipe_applies(&M) != 0;
+        P->vdec = vm_pipe && P->lanes && decode && !P->gdec && zpq_vdec_applies(&M) != 0;
+        const int cap_res = c->cus * (P->vpipe ? zpq_vpipe_blocks_per_cu(&M) : P->vdec ? zpq_vdec_blocks_per_cu(&M) : P->gpipe ? zpq_gpipe_blocks_per_cu(&M) : P->gdec ? zpq_gdec_blocks_per_cu(&M) : P->lanes ? zpq_lanes_blocks_per_cu(&M) : zpq_generic_blocks_per_cu(&M));
         if (nslots > cap_res) nslots = cap_res;
         if (!own_slot && (uint64_t)nslots > max_by_mem) nslots = (int)max_by_mem;
         grid = nslots;
@@ -552,6 +567,14 @@ static int run_batch(zpq_ctx *c, const zpq_model *m, int decode, const BatchArgs
         rc = zpq_launch_chain(&B, &M, decode, grid, bpw, c->stream, &name);
         if (rc != ZPQ_OK) return rc;
         c->last_name = name;
+    } else if (want_lanes && P.vpipe) {
+        rc = zpq_launch_vpipe(&B, &M, nslots, c->stream);
+        if (rc != ZPQ_OK) return rc;
+        c->last_name = "k_vpipe<encode>";
+    } else if (want_lanes && P.vdec) {
+        rc = zpq_launch_vdec(&B, &M, nslots, c->stream);
+        if (rc != ZPQ_OK) return rc;
+        c->last_name = "k_vdec<decode>";
     } else if (want_lanes && P.gpipe) {
         rc = zpq_launch_gpipe(&B, &M, nslots, c->stream);
         if (rc != ZPQ_OK) return rc;
@@ -1096,7 +1119,7 @@ extern "C" int zpq_block_encode_segment(zpq_block *b, const uint8_t *in, size_t 
     uint32_t olen = 0;
     int32_t st = 0;
     if (b->fresh && !(flags & ZPQ_FLAG_GENERIC)) {
-        int rc = host_batch(b->ctx, b->model, 0, 1, in, in_off, flags & 0xffu, out, out_off, &olen, nullptr, nullptr,
+        int rc = host_batch(b->ctx, b->model, 0, 1, in, in_off, (flags & 0xffu) | ZB_NO_VMPIPE, out, out_off, &olen, nullptr, nullptr,
                             nullptr, &st, nullptr, nullptr, 0, nullptr, 0);
         if (rc != ZPQ_OK) return rc;
         *out_len = olen;
@@ -1127,7 +1150,7 @@ extern "C" int zpq_block_decode_segment(zpq_block *b, const uint8_t *in, size_t 
     uint32_t olen = 0, cons = 0, code = 0, first = 0xFFFFFFFFu;
     int32_t st = 0;
     if (b->fresh && !(flags & ZPQ_FLAG_GENERIC)) {
-        int rc = host_batch(b->ctx, b->model, 1, 1, in, in_off, flags & 0xffu, out, out_off, &olen, &cons, &code, &first,
+        int rc = host_batch(b->ctx, b->model, 1, 1, in, in_off, (flags & 0xffu) | ZB_NO_VMPIPE, out, out_off, &olen, &cons, &code, &first,
                             &st, nullptr, nullptr, 0, nullptr, 0);
         if (rc != ZPQ_OK) return rc;
         *out_len = olen;

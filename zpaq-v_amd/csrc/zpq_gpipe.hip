@@ -28,9 +28,14 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <map>
+#include <mutex>
+#include <tuple>
+
 #include "../../include/zpaq_hip.h"
 #include "zpq_common.h"
 #include "zpq_host.h"
+#include "zpq_vm.h"
 
 namespace zpqg {
 
@@ -91,6 +96,8 @@ struct Stage {
     u32 nin, total, iters;
     u8 *dst;
     u32 cap;
+    const u32 *vctx;             // (k_vpipe) this component's ring of contexts, at this lane: byte b's H[ci] at (b & vmask) * BPW
+    u32 vmask;
 };
 
 // the eight predictions of one byte, packed
@@ -111,7 +118,8 @@ struct P8 {
 
 // One component wave.  The per-bit code is the reference's predict() + update() for this component's type, restated on
 // the block's tables in HBM (predictor.v:536-824; the CPU oracle's pred_predict / pred_update are the same text).
-template <int TYPE, bool BATCH>
+// VM: the context of a byte comes from the ring the interpreter wave fills (k_vpipe), not from the hash chain in registers.
+template <int TYPE, bool BATCH, bool VM = false>
 __device__ __forceinline__ void comp_stage(const Stage &S)
 {
     const DBatch &B = *S.B;
@@ -184,6 +192,7 @@ __device__ __forceinline__ void comp_stage(const Stage &S)
                 if (bi + 1u < total && (a1 & ~(uintptr_t)3) != (a & ~(uintptr_t)3)) w_cur = *reinterpret_cast<const u32 *>(a1 & ~(uintptr_t)3);
                 s_bytes[(bi & 15u) * BPW + S.lane] = (u8)ch;
             } else ch = s_bytes[(bi & 15u) * BPW + S.lane];
+            if (VM) hctx = S.vctx[(bi & S.vmask) * BPW];
             // inputs: the predictions of this byte by the components this one names (all earlier ones)
             P8 in0 = {0, 0, 0, 0}, in1 = {0, 0, 0, 0};
             P8 inm[8];
@@ -603,7 +612,7 @@ __device__ __forceinline__ void comp_stage(const Stage &S)
             }
             }
             *ring_at(ci, bi) = make_uint4(out.a, out.b, out.c, out.d);
-            {   // ZPAQL.run(byte) of the shipped hash chain: H[ci] for the next byte
+            if (!VM) {  // ZPAQL.run(byte) of the shipped hash chain: H[ci] for the next byte
                 u32 a = ch;
                 for (u32 k = 0; k < hash_steps; k++) a = (a + prev + 512u) * 773u;
                 hctx = hash_steps ? a : 0u;
@@ -810,9 +819,11 @@ struct DStage {
     u32 cap;
     int blk;
     u64 prof[4];                 // (-DZPG_PROF) cycles: loads in, levels, waiting for the bit, training
+    const u32 *vctx;             // (k_vdec) H[ci] of this lane's block, left by the interpreter wave before the byte's first barrier
 };
 
-template <int TYPE>
+// VM: the context of a byte is read from LDS (k_vdec), not computed by the hash chain in registers.
+template <int TYPE, bool VM = false>
 __device__ __forceinline__ void comp_dec(const DStage &S)
 {
     const DModel &M = *S.M;
@@ -886,6 +897,7 @@ __device__ __forceinline__ void comp_dec(const DStage &S)
         lds_barrier();                                           // the decoder wave has looked at the EOF flag
         const bool alive = S.active && s_alive[S.lane] != 0;
         if (*s_any == 0) break;
+        if (VM) hctx = *S.vctx;
         u32 c8 = 1, hmap4 = 1;
 #pragma unroll 1
         for (int kb = 0; kb < 8; kb++) {
@@ -1150,7 +1162,7 @@ __device__ __forceinline__ void comp_dec(const DStage &S)
             } else if (ma < 255) ma++;
             cm[cmi] = (u32)mlimit;
         }
-        {
+        if (!VM) {
             u32 a = byte;
             for (u32 k = 0; k < hash_steps; k++) a = (a + prev + 512u) * 773u;
             hctx = hash_steps ? a : 0u;
@@ -1322,17 +1334,254 @@ __global__ void __launch_bounds__(1024) k_gdec(const DBatch B, const GCfg cfg)
     }
 }
 
+
+// ================================================================================================================
+// The same two pipelines for ANY HCOMP program: k_vpipe / k_vdec = k_gpipe / k_gdec plus one wave that runs the ZPAQL
+// interpreter (zpq_vm.h), lane = block, 64 interpreters per wave.  The component stages are the ones above; they take the
+// byte's context from LDS instead of walking the hash chain in registers (comp_stage / comp_dec with VM = true).  The
+// interpreter's a b c d f live in the wave's registers, M, H and R in the block's slot where zpq_lanes.hip keeps them, the
+// header in LDS (once per workgroup).  A run that hits ZPQ_VM_STEP_CAP marks its block ZPQ_E_VMSTEPS (sticky, ahead of
+// ZPQ_E_OVERFLOW); the lane codes on with whatever the cut run left in H, its neighbours do not notice.
+struct VCfg {
+    GCfg g;
+    uint16_t coff[16];           // encoder: component i's ring of contexts starts here (units of BPW words) ...
+    uint16_t cmask[16];          // ... and keeps cmask[i] + 1 bytes: a power of two >= i + 2
+    int32_t ctx_off;             // LDS offsets: the contexts (encoder: the rings; decoder: u32 h[n][BPW]),
+    int32_t stat_off;            // i32 vm_status[BPW],
+    int32_t hdr_off;             // the header
+};
+
+__device__ __forceinline__ void vm_bind(zpqvm::Vm &z, const DModel &M, u8 *slot, const u8 *hdr)
+{
+    z.a = z.b = z.c = z.d = 0; z.f = 0; z.pc = 0; z.out = nullptr;
+    z.m = slot + M.m_off; z.mlen = M.mlen;
+    z.h = reinterpret_cast<u32 *>(slot + M.h_off); z.hlen = M.hlen;
+    z.r = reinterpret_cast<u32 *>(slot + M.r_off);
+    z.hdr = hdr; z.hdr_len = M.hdr_len; z.hbegin = M.hbegin; z.hend = M.hend;
+}
+
+// The interpreter wave of the encoder.  In iteration `it` it runs the program on byte `it` (the PP byte is a byte like any
+// other) and leaves H[i], i < n, as the context of byte it + 1 in component i's ring; component wave i reads it in iteration
+// it + 1 + i.  Component i's ring therefore holds bytes it - i .. it + 1: i + 2 entries.  Returns the block's status.
+__device__ __forceinline__ i32 vm_stage(const Stage &S, const VCfg &V)
+{
+    const DModel &M = *S.M;
+    zpqvm::Vm z;
+    vm_bind(z, M, S.slot, S.lds + V.hdr_off);
+    u32 *const ctx = reinterpret_cast<u32 *>(S.lds + V.ctx_off) + S.lane;
+    const bool pp = (S.B->flags & ZPQ_FLAG_PP) != 0;
+    const u32 total = S.total;
+    auto byte_at = [&](const u32 bi) -> u32 { return (pp && bi == 0) ? 0u : S.src[pp ? bi - 1u : bi]; };
+    i32 status = ZPQ_OK;
+    u32 nxt = (S.active && total) ? byte_at(0) : 0u;
+    for (u32 it = 0; it < S.iters; it++) {
+        if (S.active && it < total) {
+            const u32 ch = nxt;
+            if (it + 1u < total) nxt = byte_at(it + 1u);         // (asked for a byte early)
+            if (!zpqvm::vm_run(z, ch)) status = ZPQ_E_VMSTEPS;
+            for (int i = 0; i < S.n; i++)
+                ctx[((u32)V.coff[i] + ((it + 1u) & (u32)V.cmask[i])) * BPW] = (u32)i < M.hlen ? z.h[i] : 0u;
+        }
+        lds_barrier();
+    }
+    return status;
+}
+
+template <bool BATCH>
+__global__ void __launch_bounds__(1024) k_vpipe(const DBatch B, const VCfg V)
+{
+    extern __shared__ __align__(16) u8 lds[];
+    const DModel &M = *B.model;
+    const GCfg &cfg = V.g;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    {
+        u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
+        for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
+        u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
+        for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
+        for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
+        u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
+        for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
+        int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
+        for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
+        for (int i = tid; i < M.hdr_len && i < ZPQ_MAX_HDR; i += nthr) lds[V.hdr_off + i] = M.header[i];
+    }
+    __syncthreads();
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = cfg.n;                                         // waves 0 .. n - 1: the components, n: the coder, n + 1: the interpreter
+    const int wg_slot0 = blockIdx.x * BPW;
+    const int nslots = B.nslots;
+    const int slot_id = wg_slot0 + lane;
+    const bool lane_on = slot_id < nslots;
+    u8 *const slot = B.slots + (u64)(lane_on ? slot_id : wg_slot0) * M.slot_bytes;
+    u32 *const misc = reinterpret_cast<u32 *>(lds + L_LINK + (size_t)cfg.ring * BPW * 16);
+    u32 *const s_ctx = reinterpret_cast<u32 *>(lds + V.ctx_off);
+    i32 *const s_stat = reinterpret_cast<i32 *>(lds + V.stat_off);
+    const int nctx = (V.stat_off - V.ctx_off) / 4;
+    const int wg_slots = min(BPW, nslots - wg_slot0);
+
+    for (int base = wg_slot0; base < B.nblocks; base += nslots) {
+        const int blk = base + lane;
+        const bool active = lane_on && blk < B.nblocks;
+        const int nact = min(wg_slots, B.nblocks - base);
+        init_slots(B, M, n, wg_slot0, nact, tid, nthr);          // (zeroes M, H and R with the rest of the slot: ZPAQL.clear)
+        for (int i = tid; i < nctx; i += nthr) s_ctx[i] = 0u;    // byte 0 is coded under contexts of 0
+        if (tid == 0) *misc = 0u;
+        __threadfence();
+        __syncthreads();
+
+        Stage S;
+        S.B = &B; S.M = &M; S.lds = lds; S.ci = wave; S.lane = lane; S.n = n; S.cfg = &cfg; S.active = active;
+        S.slot = slot;
+        S.src = active ? B.in + B.in_off[blk] : B.in;
+        S.nin = active ? (u32)(B.in_off[blk + 1] - B.in_off[blk]) : 0u;
+        S.dst = active ? B.out + B.out_off[blk] : B.out;
+        S.cap = active ? (u32)(B.out_off[blk + 1] - B.out_off[blk]) : 0u;
+        S.total = active ? S.nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u) : 0u;
+        if (wave == 0) atomicMax(misc, S.total);
+        __syncthreads();
+        S.iters = *misc + (u32)n;
+        S.hashes = 0;
+        S.busy = 0;
+        S.vctx = s_ctx + (wave < n ? (int)V.coff[wave] : 0) * BPW + lane;
+        S.vmask = wave < n ? (u32)V.cmask[wave] : 0u;
+        u32 opos = 0;
+        if (wave < n) {
+            switch (M.comp[wave].type) {                         // uniform per wave
+            case ZT_CONST: comp_stage<ZT_CONST, BATCH, true>(S); break;
+            case ZT_CM: comp_stage<ZT_CM, BATCH, true>(S); break;
+            case ZT_ICM: comp_stage<ZT_ICM, BATCH, true>(S); break;
+            case ZT_MATCH: comp_stage<ZT_MATCH, BATCH, true>(S); break;
+            case ZT_AVG: comp_stage<ZT_AVG, BATCH, true>(S); break;
+            case ZT_MIX2: comp_stage<ZT_MIX2, BATCH, true>(S); break;
+            case ZT_MIX: comp_stage<ZT_MIX, BATCH, true>(S); break;
+            case ZT_ISSE: comp_stage<ZT_ISSE, BATCH, true>(S); break;
+            default: comp_stage<ZT_SSE, BATCH, true>(S); break;
+            }
+        } else if (wave == n) opos = coder_stage(S);
+        else s_stat[lane] = vm_stage(S, V);
+        __syncthreads();
+        if (wave == n && active) {
+            const i32 vst = s_stat[lane];
+            B.out_len[blk] = opos;
+            B.status[blk] = vst != ZPQ_OK ? vst : (opos > S.cap ? ZPQ_E_OVERFLOW : ZPQ_OK);
+        }
+        __syncthreads();
+    }
+}
+
+// The interpreter wave of the decoder: it keeps step with the bits (the same barriers as every wave), collects the byte
+// from the decoder wave's bits and, at the byte's end, runs the program for every lane whose block was alive in that byte;
+// H[0 .. n) goes to LDS before the next byte's first barrier, behind which the component waves read it.  A wave of its
+// own rather than the decoder wave: the run then overlaps the decoder wave's output byte, EOF flag and refill and the
+// MATCH wave's search at the byte boundary, and the interpreter's registers stay out of the decoder wave's.
+__device__ __forceinline__ i32 vm_dec(const DStage &S, const VCfg &V)
+{
+    const DModel &M = *S.M;
+    u8 *const lds = S.lds;
+    zpqvm::Vm z;
+    vm_bind(z, M, S.slot, lds + V.hdr_off);
+    const u32 *const s_y = reinterpret_cast<const u32 *>(lds + D_Y);
+    const u32 *const s_alive = reinterpret_cast<const u32 *>(lds + D_ALIVE);
+    const u32 *const s_any = reinterpret_cast<const u32 *>(lds + D_ANY);
+    u32 *const s_h = reinterpret_cast<u32 *>(lds + V.ctx_off) + S.lane;
+    const int nlev = V.g.nlevels;
+    i32 status = ZPQ_OK;
+    for (;;) {
+        lds_barrier();
+        const bool alive = S.active && s_alive[S.lane] != 0;
+        if (*s_any == 0) break;
+        u32 c8 = 1;
+#pragma unroll 1
+        for (int kb = 0; kb < 8; kb++) {
+            for (int lv = 0; lv < nlev; lv++) lds_barrier();
+            lds_barrier();                                       // the decoder wave has the bit
+            c8 = (c8 << 1) | (s_y[S.lane] & 1u);
+        }
+        if (alive) {                                             // (a block that has ended runs no interpreter)
+            if (!zpqvm::vm_run(z, c8 - 256u)) status = ZPQ_E_VMSTEPS;
+            for (int i = 0; i < S.n; i++) s_h[i * BPW] = (u32)i < M.hlen ? z.h[i] : 0u;
+        }
+    }
+    return status;
+}
+
+__global__ void __launch_bounds__(1024) k_vdec(const DBatch B, const VCfg V)
+{
+    extern __shared__ __align__(16) u8 lds[];
+    const DModel &M = *B.model;
+    const GCfg &cfg = V.g;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    {
+        u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
+        for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
+        u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
+        for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
+        for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
+        u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
+        for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
+        int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
+        for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
+        for (int i = tid; i < M.hdr_len && i < ZPQ_MAX_HDR; i += nthr) lds[V.hdr_off + i] = M.header[i];
+    }
+    __syncthreads();
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = cfg.n;                                         // waves 0 .. n - 1: the components, n: the decoder, n + 1: the interpreter
+    const int wg_slot0 = blockIdx.x * cfg.bpw;
+    const int nslots = B.nslots;
+    const int slot_id = wg_slot0 + lane;
+    const bool lane_on = lane < cfg.bpw && slot_id < nslots;
+    u8 *const slot = B.slots + (u64)(lane_on ? slot_id : wg_slot0) * M.slot_bytes;
+    u32 *const s_h = reinterpret_cast<u32 *>(lds + V.ctx_off);
+    i32 *const s_stat = reinterpret_cast<i32 *>(lds + V.stat_off);
+    const int wg_slots = min(cfg.bpw, nslots - wg_slot0);
+
+    for (int base = wg_slot0; base < B.nblocks; base += nslots) {
+        const int blk = base + lane;
+        const bool active = lane_on && blk < B.nblocks;
+        const int nact = min(wg_slots, B.nblocks - base);
+        init_slots(B, M, n, wg_slot0, nact, tid, nthr);
+        for (int i = tid; i < n * BPW; i += nthr) s_h[i] = 0u;   // the first byte is decoded under contexts of 0
+        __threadfence();
+        __syncthreads();
+        DStage S;
+        S.B = &B; S.M = &M; S.lds = lds; S.cfg = &cfg; S.ci = wave; S.lane = lane; S.n = n; S.active = active; S.slot = slot; S.blk = blk;
+        S.src = active ? B.in + B.in_off[blk] : B.in;
+        S.nin = active ? (u32)(B.in_off[blk + 1] - B.in_off[blk]) : 0u;
+        S.dst = active ? B.out + B.out_off[blk] : B.out;
+        S.cap = active ? (u32)(B.out_off[blk + 1] - B.out_off[blk]) : 0u;
+        S.prof[0] = S.prof[1] = S.prof[2] = S.prof[3] = 0;
+        S.vctx = s_h + (wave < n ? wave : 0) * BPW + lane;
+        if (wave < n) {
+            switch (M.comp[wave].type) {                         // uniform per wave
+            case ZT_CONST: comp_dec<ZT_CONST, true>(S); break;
+            case ZT_CM: comp_dec<ZT_CM, true>(S); break;
+            case ZT_ICM: comp_dec<ZT_ICM, true>(S); break;
+            case ZT_MATCH: comp_dec<ZT_MATCH, true>(S); break;
+            case ZT_AVG: comp_dec<ZT_AVG, true>(S); break;
+            case ZT_MIX2: comp_dec<ZT_MIX2, true>(S); break;
+            case ZT_MIX: comp_dec<ZT_MIX, true>(S); break;
+            case ZT_ISSE: comp_dec<ZT_ISSE, true>(S); break;
+            default: comp_dec<ZT_SSE, true>(S); break;
+            }
+        } else if (wave == n) coder_dec(S);
+        else s_stat[lane] = vm_dec(S, V);
+        __syncthreads();
+        if (wave == n && active && s_stat[lane] != ZPQ_OK) B.status[blk] = s_stat[lane];   // (sticky: ahead of the decoder wave's ZPQ_E_OVERFLOW)
+        __syncthreads();
+    }
+}
+
 }  // namespace zpqg
 
 // ------------------------------------------------------------------ host side
-// The pipeline takes a model when every component is one of the nine types, names only EARLIER components as inputs, the
-// HCOMP program is the shipped hash chain with a hash per component, and the rings fit the LDS.
-static bool gpipe_cfg(const DModel *M, zpqg::GCfg *cfg, size_t *lds_bytes, size_t *dec_lds = nullptr)
+// The structure both pairs of pipelines ask for, whatever the HCOMP program: every component is one of the nine types and
+// names only EARLIER components as inputs, a MIX has 1-8 of them, a MATCH a buffer of two bytes or more.  Fills the
+// rings, levels and SSE rows of cfg and the LDS either direction needs without an interpreter; cfg->hashes stays 0.
+static bool pipe_structure(const DModel *M, zpqg::GCfg *cfg, size_t *lds_bytes, size_t *dec_lds)
 {
     const int n = M->n;
     if (n < 1 || n > 15) return false;
-    const int hashes = zpq_vm_hashchain(M);
-    if (hashes <= 0) return false;
     int far[16];                                                 // distance from a component to its farthest consumer
     for (int i = 0; i < n; i++) far[i] = 0;
     far[n - 1] = 1;                                              // the coder
@@ -1360,7 +1609,7 @@ static bool gpipe_cfg(const DModel *M, zpqg::GCfg *cfg, size_t *lds_bytes, size_
         cfg->roff[i] = (uint16_t)total; cfg->rmask[i] = (uint16_t)(depth - 1);
         total += depth;
     }
-    cfg->n = n; cfg->ring = total; cfg->hashes = hashes;
+    cfg->n = n; cfg->ring = total;
     int nsse = 0, nlev = 1;
     for (int i = 0; i < n; i++) {                                // (inputs are earlier components: one pass)
         const DComp &c = M->comp[i];
@@ -1380,7 +1629,55 @@ static bool gpipe_cfg(const DModel *M, zpqg::GCfg *cfg, size_t *lds_bytes, size_
     cfg->nlevels = nlev;
     if (dec_lds) *dec_lds = (size_t)zpqg::D_SSE + (size_t)nsse * zpqg::D_SSE_BYTES;
     *lds_bytes = (size_t)zpqg::L_LINK + (size_t)total * zpqg::BPW * 16 + 16;
+    return true;
+}
+
+// The pipeline takes a model when it has that structure, the HCOMP program is the shipped hash chain with a hash per
+// component, and the rings fit the LDS.
+static bool gpipe_cfg(const DModel *M, zpqg::GCfg *cfg, size_t *lds_bytes, size_t *dec_lds = nullptr)
+{
+    const int hashes = zpq_vm_hashchain(M);
+    if (hashes <= 0) return false;
+    size_t dlds = 0;
+    if (!pipe_structure(M, cfg, lds_bytes, &dlds)) return false;
+    cfg->hashes = hashes;
+    if (dec_lds) *dec_lds = dlds;
     return *lds_bytes <= 160 * 1024;
+}
+
+// k_vpipe / k_vdec take a model of the same structure whose program is NOT that hash chain (those keep k_gpipe / k_gdec),
+// with n <= 14 (n + 2 waves in 1024 threads; one bound for both directions) and, on top of what k_gpipe / k_gdec keep in
+// LDS, the contexts, a status word per lane and the header:
+//   encoder: L_LINK + 1024 * ring + 16 + 256 * ctx + 256 + hdr      ring = sum over the components of their prediction rings
+//                                                                    ctx  = sum over i < n of (the power of two >= i + 2)
+//   decoder: D_SSE + 9216 * (number of SSEs) + 256 * n + 256 + hdr  hdr  = the header's length rounded up to 16
+// both at most 160 KiB.
+static bool vpipe_cfg(const DModel *M, zpqg::VCfg *V, size_t *lds_bytes, size_t *dec_lds)
+{
+    memset(V, 0, sizeof *V);
+    if (M->n > 14 || zpq_vm_hashchain(M) > 0) return false;
+    if (M->hdr_len < 0 || M->hdr_len > ZPQ_MAX_HDR) return false;
+    size_t enc = 0, dec = 0;
+    if (!pipe_structure(M, &V->g, &enc, &dec)) return false;
+    int ctx = 0;
+    for (int i = 0; i < M->n; i++) {
+        int depth = 2;
+        while (depth < i + 2) depth *= 2;
+        V->coff[i] = (uint16_t)ctx; V->cmask[i] = (uint16_t)(depth - 1);
+        ctx += depth;
+    }
+    const size_t hdr = ((size_t)M->hdr_len + 15) & ~(size_t)15;
+    *lds_bytes = enc + (size_t)ctx * zpqg::BPW * 4 + zpqg::BPW * 4 + hdr;
+    *dec_lds = dec + (size_t)M->n * zpqg::BPW * 4 + zpqg::BPW * 4 + hdr;
+    return *lds_bytes <= 160 * 1024 && *dec_lds <= 160 * 1024;
+}
+// (the two layouts differ: the offsets are set for the direction that is launched)
+static void vpipe_offsets(zpqg::VCfg *V, size_t lds_total, int ctx_words, int hdr_len)
+{
+    const size_t hdr = ((size_t)hdr_len + 15) & ~(size_t)15;
+    V->hdr_off = (int32_t)(lds_total - hdr);
+    V->stat_off = V->hdr_off - zpqg::BPW * 4;
+    V->ctx_off = V->stat_off - ctx_words * 4;
 }
 
 // ZPQ_ENC_GPIPE=0 keeps general models on zpq_lanes.hip (tests compare the two)
@@ -1475,5 +1772,92 @@ extern "C" int zpq_launch_gdec(const DBatch *B, const DModel *hostM, int nslots,
     const int nwg = (nslots + bpw - 1) / bpw;
     (void)hipFuncSetAttribute((const void *)zpqg::k_gdec, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipLaunchKernelGGL(zpqg::k_gdec, dim3(nwg), dim3(64 * (cfg.n + 1)), dlds, stream, *B, cfg);
+    return ZPQ_OK;
+}
+
+// ---- any HCOMP program on the wave pipelines (k_vpipe / k_vdec), on request: ZPQ_FLAG_VMPIPE / ZPQ_VM_PIPE
+extern "C" int zpq_vpipe_applies(const DModel *M)
+{
+    zpqg::VCfg V;
+    size_t lds = 0, dlds = 0;
+    return vpipe_cfg(M, &V, &lds, &dlds) ? 1 : 0;
+}
+
+extern "C" int zpq_vdec_applies(const DModel *M) { return zpq_vpipe_applies(M); }   // (one envelope for both directions)
+
+// The occupancy answer of these kernels, asked once per (kernel, threads, LDS) and device, then kept.
+static int vpipe_occupancy(const void *fn, int threads, size_t lds, int bound)
+{
+    struct Key {
+        const void *fn; int dev, threads; size_t lds; int bound;
+        bool operator<(const Key &o) const { return std::tie(fn, dev, threads, lds, bound) < std::tie(o.fn, o.dev, o.threads, o.lds, o.bound); }
+    };
+    static std::mutex mu;
+    static std::map<Key, int> known;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return bound; }
+    const Key k{fn, dev, threads, lds, bound};
+    std::lock_guard<std::mutex> g(mu);
+    auto it = known.find(k);
+    if (it == known.end()) it = known.emplace(k, occupancy_wgs(fn, threads, lds, bound)).first;
+    return it->second;
+}
+
+static int vpipe_wgs_bound(int n, size_t lds)
+{
+    const int wgs = (int)((160 * 1024) / lds), by_waves = 16 / (n + 2);   // n + 2 of the 16 waves that 128 VGPRs allow
+    const int w = wgs < by_waves ? wgs : by_waves;
+    return w < 1 ? 1 : w;
+}
+
+extern "C" int zpq_vpipe_blocks_per_cu(const DModel *M)
+{
+    zpqg::VCfg V;
+    size_t lds = 0, dlds = 0;
+    if (!vpipe_cfg(M, &V, &lds, &dlds)) return 0;
+    const int w = vpipe_wgs_bound(V.g.n, lds), threads = 64 * (V.g.n + 2);
+    const int a = vpipe_occupancy((const void *)zpqg::k_vpipe<true>, threads, lds, w), b = vpipe_occupancy((const void *)zpqg::k_vpipe<false>, threads, lds, w);
+    return (a < b ? a : b) * zpqg::BPW;
+}
+
+extern "C" int zpq_vdec_blocks_per_cu(const DModel *M)
+{
+    zpqg::VCfg V;
+    size_t lds = 0, dlds = 0;
+    if (!vpipe_cfg(M, &V, &lds, &dlds)) return 0;
+    return vpipe_occupancy((const void *)zpqg::k_vdec, 64 * (V.g.n + 2), dlds, vpipe_wgs_bound(V.g.n, dlds)) * zpqg::BPW;
+}
+
+extern "C" int zpq_launch_vpipe(const DBatch *B, const DModel *hostM, int nslots, hipStream_t stream)
+{
+    zpqg::VCfg V;
+    size_t lds = 0, dlds = 0;
+    if (!vpipe_cfg(hostM, &V, &lds, &dlds)) return ZPQ_E_INTERNAL;
+    vpipe_offsets(&V, lds, (int)(V.coff[V.g.n - 1] + V.cmask[V.g.n - 1] + 1) * zpqg::BPW, hostM->hdr_len);
+    const int nwg = (nslots + zpqg::BPW - 1) / zpqg::BPW;
+    const char *ev = getenv("ZPQ_GPIPE_BATCH");                   // "0": the bit-serial stages, as for k_gpipe
+    if (ev && atoi(ev) == 0) {
+        (void)hipFuncSetAttribute((const void *)zpqg::k_vpipe<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipLaunchKernelGGL(zpqg::k_vpipe<false>, dim3(nwg), dim3(64 * (V.g.n + 2)), lds, stream, *B, V);
+    } else {
+        (void)hipFuncSetAttribute((const void *)zpqg::k_vpipe<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipLaunchKernelGGL(zpqg::k_vpipe<true>, dim3(nwg), dim3(64 * (V.g.n + 2)), lds, stream, *B, V);
+    }
+    return ZPQ_OK;
+}
+
+extern "C" int zpq_launch_vdec(const DBatch *B, const DModel *hostM, int nslots, hipStream_t stream)
+{
+    zpqg::VCfg V;
+    size_t lds = 0, dlds = 0;
+    if (!vpipe_cfg(hostM, &V, &lds, &dlds)) return ZPQ_E_INTERNAL;
+    vpipe_offsets(&V, dlds, V.g.n * zpqg::BPW, hostM->hdr_len);
+    const char *ev = getenv("ZPQ_GDEC_BPW");                      // as for k_gdec
+    int bpw = zpqg::BPW;
+    if (ev && (atoi(ev) == 16 || atoi(ev) == 32 || atoi(ev) == 64)) bpw = atoi(ev);
+    V.g.bpw = bpw;
+    const int nwg = (nslots + bpw - 1) / bpw;
+    (void)hipFuncSetAttribute((const void *)zpqg::k_vdec, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL(zpqg::k_vdec, dim3(nwg), dim3(64 * (V.g.n + 2)), dlds, stream, *B, V);
     return ZPQ_OK;
 }
