@@ -267,11 +267,32 @@ int zpq_block_decode_segment(zpq_block *, const uint8_t *in, size_t n, uint32_t 
  * A member whose segment ends with a status other than ZPQ_OK (ZPQ_E_OVERFLOW, ZPQ_E_TOOBIG, ZPQ_E_VMSTEPS) has FAILED:
  * later calls report that status for it without coding, the other members are untouched.  ZPQ_FLAG_NOEOF: ZPQ_E_ARG.
  * Lifetime as for zpq_block: the ctx orphans its sets (calls then return ZPQ_E_CLOSED), a set keeps its model alive.
+ *
+ * Models no chain kernel takes are coded by the lane-0 kernel, ONE LAUNCH PER MEMBER.  zpq_blockset_create_ex /
+ * zpq_blockset_capacity_ex take flags (unknown bits: ZPQ_E_ARG); the plain forms are the _ex forms with flags = 0.
+ *   ZPQ_SET_LANES         a request: code such a model on the lane-per-component kernels (k_rows / k_lanes, a state
+ *                         hand-over form of each), one launch per round whatever the number of members.  Honoured when
+ *                         zpq_blockset_lanes_applies(model): no chain kernel takes it and it has at most 64 components.
+ *                         Otherwise it decides nothing.  The capacity of such a set is bounded by memory alone.  It keeps
+ *                         p[], the last bit's predictions, across segments as the reference does; the lane-0 kernel
+ *                         starts every segment with p[] = 0, which differs only for a component whose input index is not
+ *                         below its own.  The environment variable ZPQ_SET_LANES=1 makes the request for every set the
+ *                         process creates, ZPQ_SET_LANES=0 withdraws it (anything but a leading 0 / 1 decides nothing).
+ *   zpq_blockset_flags    the ZPQ_SET_* in force for a set (0 for a request that decided nothing).  Like every call on a
+ *                         set it must not race with zpq_blockset_destroy of the same handle.
+ *   zpq_blockset_lanes_applies / zpq_blockset_resolve_flags   host logic only, no device needed: would the request be
+ *                         honoured for this model; the flags a set created with `flags` would get (environment applied).
  */
+#define ZPQ_SET_LANES 1u
 typedef struct zpq_blockset zpq_blockset;
 int zpq_blockset_create(zpq_ctx *, const zpq_model *, int nmembers, uint64_t max_member_bytes, zpq_blockset **out);
+int zpq_blockset_create_ex(zpq_ctx *, const zpq_model *, int nmembers, uint64_t max_member_bytes, uint32_t flags, zpq_blockset **out);
 void zpq_blockset_destroy(zpq_blockset *);
 int zpq_blockset_capacity(zpq_ctx *, const zpq_model *, uint64_t max_member_bytes);
+int zpq_blockset_capacity_ex(zpq_ctx *, const zpq_model *, uint64_t max_member_bytes, uint32_t flags);
+unsigned zpq_blockset_flags(const zpq_blockset *);
+int zpq_blockset_lanes_applies(const zpq_model *);
+int zpq_blockset_resolve_flags(const zpq_model *, uint32_t flags);
 int zpq_blockset_encode_segments(zpq_blockset *, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
                                  uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status);
 int zpq_blockset_decode_segments(zpq_blockset *, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,

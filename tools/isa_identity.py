@@ -2,7 +2,8 @@
 (llvm-objdump, no GPU needed) and compares, per kernel symbol, the list of instructions with their operands.
     python tools/isa_identity.py OLD.so NEW.so [name filter ...]      (default filters: k_chain k_pipe)
 A k_chain symbol of OLD that NEW lacks is looked up with one more `false` template argument (a parameter added at the end
-with a default).  What follows a kernel's last s_endpgm is no code -- s_nop fill up to the next symbol's alignment, the
+with a default); a k_lanes / k_rows symbol with `false` in front of its last template argument (KEEP, added before VMH, which
+stays last).  What follows a kernel's last s_endpgm is no code -- s_nop fill up to the next symbol's alignment, the
 prefetch guard behind the module's last function, objdump's `...` for a run of it -- and depends on which function comes
 next, so it is left out of the comparison.  Prints the kernels that differ with their per-opcode count changes, then the totals."""
 import collections
@@ -58,7 +59,12 @@ def main():
     for name, ia in sorted(old.items()):
         if not any(f in name for f in filters):
             continue
-        other = name if name in new else name.replace("EEEv6DBatch", "ELb0EEEv6DBatch")
+        if name in new:
+            other = name
+        elif "k_lanes" in name or "k_rows" in name:
+            other = re.sub(r"(Lb[01]E)(Lb[01]EEEv6DBatch)", r"\1Lb0E\2", name)
+        else:
+            other = name.replace("EEEv6DBatch", "ELb0EEEv6DBatch")
         if other not in new:
             print("missing in the new build:", name)
             diff += 1

@@ -32,6 +32,8 @@
 extern "C" void zpq_launch_generic(const DBatch *B, const DModel *hostM, int decode, int grid, hipStream_t stream);
 extern "C" int zpq_generic_blocks_per_cu(const DModel *M);
 extern "C" int zpq_lanes_supported(const DModel *M);
+extern "C" int zpq_launch_lanes_set_init(const DModel *d_model, const uint32_t *d_img, uint8_t *slots, int nmembers, hipStream_t stream);
+extern "C" int zpq_launch_lanes_keep(const DBatch *B, const DModel *hostM, int decode, hipStream_t stream);
 extern "C" int zpq_lanes_blocks_per_cu(const DModel *M);
 extern "C" int zpq_launch_lanes(const DBatch *B, const DModel *hostM, int decode, int nslots, hipStream_t stream);
 extern "C" const char *zpq_lanes_kernel_name(const DModel *M, int decode);   // k_rows (four blocks per wave) or k_lanes
@@ -196,12 +198,14 @@ struct zpq_block {
 
 // N blocks whose model state persists across segments, coded a segment of each per launch (zpq_blockset_*).  The state
 // lives in the set's own slots, in the layout chosen when the set is made: chain models on k_chain<..., KEEP> (dense tables
-// or the line store, sized by max_member_bytes), every other model on k_generic with ZB_KEEP_STATE, a launch per member.
+// or the line store, sized by max_member_bytes), every other model on k_generic with ZB_KEEP_STATE, a launch per member --
+// or, on request (ZPQ_SET_LANES) and with at most 64 components, on the KEEP forms of k_rows / k_lanes, a launch per round.
 struct zpq_blockset {
     zpq_ctx *ctx = nullptr;        // nullptr once the ctx has been destroyed (orphaned set)
     const zpq_model *model = nullptr;   // the set holds a reference
     int nmembers = 0;
     bool chain = false;
+    uint32_t flags = 0;            // ZPQ_SET_* in force (a request that decides nothing is not among them)
     uint32_t sp = 0;               // line-store capacity (lines), 0 = dense tables
     DModel layout;                 // what the kernels see
     uint8_t *slots = nullptr;
@@ -1221,17 +1225,37 @@ static bool set_layout(const zpq_ctx *c, const zpq_model *m, uint64_t max_member
     return true;
 }
 
-static int set_capacity(zpq_ctx *c, const DModel &layout, bool chain)
+// ZPQ_SET_LANES, a request: honoured where no chain kernel takes the model and the lane-per-component kernels do.  The
+// environment variable ZPQ_SET_LANES=1 sets it for every set of the process, ZPQ_SET_LANES=0 clears it (anything but a
+// leading '0' or '1' decides nothing, as with ZPQ_VM_PIPE).  Host logic only: no device is needed.
+static bool set_is_chain(const zpq_model *m) { return m->d.fast_kind && zpq_chain_blocks_per_wg(&m->d) > 0; }
+extern "C" int zpq_blockset_lanes_applies(const zpq_model *m) try
+{
+    return m && !set_is_chain(m) && zpq_lanes_supported(&m->d) ? 1 : 0;
+} ZPQ_CATCH(return 0)
+extern "C" int zpq_blockset_resolve_flags(const zpq_model *m, uint32_t flags) try
+{
+    if (!m || (flags & ~(uint32_t)ZPQ_SET_LANES)) return ZPQ_E_ARG;
+    const char *ev = getenv("ZPQ_SET_LANES");
+    const bool env = ev && (ev[0] == '0' || ev[0] == '1');
+    const bool want = env ? ev[0] == '1' : (flags & ZPQ_SET_LANES) != 0;
+    return want && zpq_blockset_lanes_applies(m) ? (int)ZPQ_SET_LANES : 0;
+} ZPQ_CATCH(return ZPQ_E_INTERNAL)
+
+static int set_capacity(zpq_ctx *c, const DModel &layout, bool chain, bool lanes)
 {
     const uint64_t by_mem = layout.slot_bytes ? c->pool_budget() / layout.slot_bytes : (1u << 20);
+    // (the lane kernels have no dependency between workgroups: a launch may hold any number of members)
+    if (lanes) return by_mem > (1u << 20) ? (1 << 20) : (int)by_mem;
     const uint64_t resident = chain ? (uint64_t)zpq_chain_max_wgs(&layout, c->cus) * (uint64_t)zpq_chain_blocks_per_wg(&layout)
                                     : (uint64_t)c->cus * (uint64_t)zpq_generic_blocks_per_cu(&layout);
     const uint64_t n = by_mem < resident ? by_mem : resident;
     return n > (1u << 20) ? (1 << 20) : (int)n;
 }
 
-extern "C" int zpq_blockset_capacity(zpq_ctx *c, const zpq_model *m, uint64_t max_member_bytes) try
+extern "C" int zpq_blockset_capacity_ex(zpq_ctx *c, const zpq_model *m, uint64_t max_member_bytes, uint32_t flags) try
 {
+    if (flags & ~(uint32_t)ZPQ_SET_LANES) return ZPQ_E_ARG;
     if (!ctx_live(c)) return c ? ZPQ_E_CLOSED : ZPQ_E_ARG;
     if (!m) return ZPQ_E_ARG;
     HIPCK(hipSetDevice(c->device));
@@ -1239,13 +1263,19 @@ extern "C" int zpq_blockset_capacity(zpq_ctx *c, const zpq_model *m, uint64_t ma
     static thread_local DModel layout;
     uint32_t sp = 0;
     const bool chain = set_layout(c, m, max_member_bytes, &layout, &sp);
-    return set_capacity(c, layout, chain);
+    return set_capacity(c, layout, chain, zpq_blockset_resolve_flags(m, flags) == (int)ZPQ_SET_LANES);
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
-extern "C" int zpq_blockset_create(zpq_ctx *c, const zpq_model *m, int nmembers, uint64_t max_member_bytes, zpq_blockset **out) try
+extern "C" int zpq_blockset_capacity(zpq_ctx *c, const zpq_model *m, uint64_t max_member_bytes) try
+{
+    return zpq_blockset_capacity_ex(c, m, max_member_bytes, 0);
+} ZPQ_CATCH(return ZPQ_E_INTERNAL)
+
+extern "C" int zpq_blockset_create_ex(zpq_ctx *c, const zpq_model *m, int nmembers, uint64_t max_member_bytes, uint32_t flags, zpq_blockset **out) try
 {
     if (!out) return ZPQ_E_ARG;
     *out = nullptr;
+    if (flags & ~(uint32_t)ZPQ_SET_LANES) return ZPQ_E_ARG;
     if (!ctx_live(c)) return c ? ZPQ_E_CLOSED : ZPQ_E_ARG;
     if (!m || nmembers < 1) return ZPQ_E_ARG;
     HIPCK(hipSetDevice(c->device));
@@ -1253,9 +1283,11 @@ extern "C" int zpq_blockset_create(zpq_ctx *c, const zpq_model *m, int nmembers,
     zpq_blockset *s = new (std::nothrow) zpq_blockset();
     if (!s) return ZPQ_E_NOMEM;
     s->chain = set_layout(c, m, max_member_bytes, &s->layout, &s->sp);
+    s->flags = (uint32_t)zpq_blockset_resolve_flags(m, flags);
+    const bool lanes = (s->flags & ZPQ_SET_LANES) != 0;
     s->nmembers = nmembers;
     s->bytes = (uint64_t)nmembers * s->layout.slot_bytes + 256;
-    if (nmembers > set_capacity(c, s->layout, s->chain) || s->bytes > c->pool_budget()) { delete s; return ZPQ_E_NOMEM; }
+    if (nmembers > set_capacity(c, s->layout, s->chain, lanes) || s->bytes > c->pool_budget()) { delete s; return ZPQ_E_NOMEM; }
     if (hipMalloc((void **)&s->slots, s->bytes) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipStreamSynchronize(c->stream);
@@ -1271,6 +1303,12 @@ extern "C" int zpq_blockset_create(zpq_ctx *c, const zpq_model *m, int nmembers,
             hipLaunchKernelGGL(k_set_fill, dim3(nmembers), dim3(256), 0, c->stream, (const DModel *)dm.d_model, (const uint32_t *)dm.d_img, s->slots);
             if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = ZPQ_E_NODEVICE;
         }
+    } else if (lanes) {
+        // Predictor.init + ZPAQL.clear of every member now: each launch on the set is KEEP, the first segment's included
+        DevModel dm;
+        rc = get_dev_model(c, m, s->layout, 0, &dm);
+        if (rc == ZPQ_OK) rc = zpq_launch_lanes_set_init(dm.d_model, dm.d_img, s->slots, nmembers, c->stream);
+        if (rc == ZPQ_OK && (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) rc = ZPQ_E_NODEVICE;
     }
     if (rc != ZPQ_OK) { (void)hipGetLastError(); (void)hipFree(s->slots); delete s; return rc; }
     s->failed.assign((size_t)nmembers, ZPQ_OK);
@@ -1286,6 +1324,16 @@ extern "C" int zpq_blockset_create(zpq_ctx *c, const zpq_model *m, int nmembers,
     *out = s;
     return ZPQ_OK;
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
+
+extern "C" int zpq_blockset_create(zpq_ctx *c, const zpq_model *m, int nmembers, uint64_t max_member_bytes, zpq_blockset **out) try
+{
+    return zpq_blockset_create_ex(c, m, nmembers, max_member_bytes, 0, out);
+} ZPQ_CATCH(return ZPQ_E_INTERNAL)
+
+extern "C" unsigned zpq_blockset_flags(const zpq_blockset *s) try
+{
+    return s ? s->flags : 0u;
+} ZPQ_CATCH(return 0u)
 
 extern "C" void zpq_blockset_destroy(zpq_blockset *s) try
 {
@@ -1382,7 +1430,7 @@ static int set_segments(zpq_blockset *s, int decode, int n, const int32_t *membe
     HIPCK(hipMemsetAsync(c->s_u32[0].p, 0, u32b, st));
     uint32_t *d_len = (uint32_t *)c->s_u32[0].p, *d_cons = (uint32_t *)c->s_u32[1].p, *d_code = (uint32_t *)c->s_u32[2].p,
              *d_first = (uint32_t *)c->s_u32[3].p;
-    if (s->chain) {
+    if (s->chain || (s->flags & ZPQ_SET_LANES)) {
         DevModel dm;
         if ((rc = get_dev_model(c, s->model, s->layout, s->sp, &dm)) != ZPQ_OK) return rc;
         DBatch B;
@@ -1397,16 +1445,23 @@ static int set_segments(zpq_blockset *s, int decode, int n, const int32_t *membe
         B.squash = c->d_squash; B.stretch = c->d_stretch; B.dt = c->d_dt; B.dt2k = c->d_dt2k;
         B.ns = c->d_ns; B.stretch_c = c->d_stretch_c;
         B.slot_map = (const int32_t *)c->s_misc.p;
-        int bpw = 0;
-        if (!zpq_chain_plan(&s->layout, k, c->cus, &bpw)) return ZPQ_E_INTERNAL;
-        const int grid = (k + bpw - 1) / bpw;
-        if (grid > zpq_chain_max_wgs(&s->layout, c->cus)) return ZPQ_E_INTERNAL;   // (nmembers <= capacity rules this out)
         c->last_slots = k;
         c->last_sp = s->sp;
-        HIPCK(hipEventRecord(c->ev0, st));
-        const char *name = nullptr;
-        if ((rc = zpq_launch_chain(&B, &s->layout, decode, grid, bpw, st, &name)) != ZPQ_OK) return rc;
-        c->last_name = name;
+        if (s->chain) {
+            int bpw = 0;
+            if (!zpq_chain_plan(&s->layout, k, c->cus, &bpw)) return ZPQ_E_INTERNAL;
+            const int grid = (k + bpw - 1) / bpw;
+            if (grid > zpq_chain_max_wgs(&s->layout, c->cus)) return ZPQ_E_INTERNAL;   // (nmembers <= capacity rules this out)
+            HIPCK(hipEventRecord(c->ev0, st));
+            const char *name = nullptr;
+            if ((rc = zpq_launch_chain(&B, &s->layout, decode, grid, bpw, st, &name)) != ZPQ_OK) return rc;
+            c->last_name = name;
+        } else {
+            // the round in one launch of k_rows / k_lanes<..., KEEP>: any number of members, no workgroup waits for another
+            HIPCK(hipEventRecord(c->ev0, st));
+            if ((rc = zpq_launch_lanes_keep(&B, &s->layout, decode, st)) != ZPQ_OK) return rc;
+            c->last_name = zpq_lanes_kernel_name(&s->layout, decode);
+        }
         HIPCK(hipGetLastError());
         HIPCK(hipEventRecord(c->ev1, st));
         c->ev_valid = true;

@@ -20,7 +20,8 @@
 //      lane 0 (shared interpreter, zpq_vm.h).
 // Tables squash / compact stretch / ns / dt / dt2k live in LDS, shared by the 4 waves (blocks)
 // of a workgroup; component state stays in the block's HBM slot (same layout as
-// zpq_generic.hip, which remains the fallback for n > 64 and multi-segment blocks).
+// zpq_generic.hip, which remains the fallback for n > 64 and multi-segment blocks; block sets
+// may ask for the KEEP form of the kernels here instead: ZPQ_SET_LANES).
 //
 // Reference behaviour reproduced (file:line under the reference's zpaq/):
 //   predict predictor.v:536-668  update predictor.v:672-824  find_ht predictor.v:495-532
@@ -96,7 +97,23 @@ __device__ __forceinline__ i32 clamp512k(i32 x) { return min(max(x, -262144), 26
 
 // VMH: the program is the shipped hash chain (cfg.vm_hashes > 0), evaluated in registers -- such launches do not carry
 // the ZPAQL interpreter at all (fewer registers, no spills); any other program runs through it on lane 0.
-template <bool DEC, bool VMH>
+//
+// KEEP (block sets; k_rows below takes the same parameter): the block's state is handed from launch to launch through its slot.
+// Block i of the launch works on slot B.slot_map[i], one block per slot and launch; nothing is cleared, the block starts
+// from what the slot holds and stores back, behind the byte loop, what outlives a segment in the reference
+// (Predictor.reset only sets c8 = 1, hmap4 = 1, h[i] = 0: predictor.v:827-833) and lives in registers or LDS here:
+//   DCompScal[i]   MATCH's a / b / c / limit / cxt; pad_[0] = p[i], the last bit's prediction (the reference keeps p[]
+//                  across segments, and a component whose input index is >= its own reads it at the next first bit: Q13)
+//   DVmRegs        the interpreter's a b c d f pc; pad_[0] = the previous byte, which is all the in-register hash chain
+//                  (VMH) carries from byte to byte
+//   H              k_lanes keeps it in LDS when it fits: copied in and out, so that k_rows (H in the slot) reads the same
+//                  (not under VMH: the hash chain in registers never touches H)
+// The live bit-history rows need nothing: the byte loop writes a row to its table address at every nibble end, and a
+// segment ends on a byte boundary (the decoder's EOF and overflow breaks included).
+// MIX / MIX2 / SSE entries never stay in registers beyond the bit that fetched them.  The format is the same for both
+// kernels: ZPQ_LANES_ROWS may change between two launches on one set.
+// (VMH stays the last template parameter: tests/test_kernel_resources.py finds the hash-chain instantiations by it.)
+template <bool DEC, bool KEEP, bool VMH>
 __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const LCfg cfg)
 {
     extern __shared__ __align__(16) u8 lds[];
@@ -130,7 +147,9 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
     const bool act = lane < n;
     const int slot_id = blockIdx.x * WAVES + wave;
     const int nslots = B.nslots;
-    u8 *slot = B.slots + (u64)slot_id * M.slot_bytes;
+    // (KEEP: waves beyond the launch's blocks code nothing and do not read past the map)
+    const int slot_ix = KEEP ? (slot_id < B.nblocks ? B.slot_map[slot_id] : 0) : slot_id;
+    u8 *slot = B.slots + (u64)slot_ix * M.slot_bytes;
 
     // this lane's component (predictor.v:239-265 as Predictor.init leaves it)
     const DComp &C = M.comp[act ? lane : 0];
@@ -160,7 +179,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
     for (int blk = slot_id; slot_id < nslots && blk < B.nblocks; blk += nslots) {
         // ---- Predictor.init + ZPAQL.clear (predictor.v:325-470, zpaql.v:54-95): the wave zeroes
         //      its slot with 16-B stores, then fills the non-zero tables
-        {
+        if (!KEEP) {
             uint4 *z4 = reinterpret_cast<uint4 *>(slot);
             const u64 n16 = M.zero_bytes / 16;
             const uint4 zero = make_uint4(0, 0, 0, 0);
@@ -184,7 +203,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         }
         const bool h_in_lds = M.hlen <= (u32)W_H_WORDS;
-        if (h_in_lds) for (u32 i = lane; i < M.hlen; i += 64) hl[i] = 0;
+        if (h_in_lds && !(KEEP && VMH)) for (u32 i = lane; i < M.hlen; i += 64) hl[i] = KEEP ? reinterpret_cast<const u32 *>(slot + M.h_off)[i] : 0u;
         for (int k = 0; k < 4; k++) reinterpret_cast<u32 *>(myrow)[k] = 0;
 
         const u8 *src = B.in + B.in_off[blk];
@@ -219,6 +238,22 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
         if (DEC && lane == last)
             for (int k = 0; k < 4; k++) { u32 c = 0; if (ipos < nin) c = src[ipos++]; code = (code << 8) | c; }
         const u32 total = DEC ? 0xFFFFFFFFu : nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u);
+        DCompScal *gs = reinterpret_cast<DCompScal *>(slot + M.scal_off);
+        DVmRegs *gr = reinterpret_cast<DVmRegs *>(slot + M.regs_off);
+        if (KEEP) {                                               // what the last segment's launch left in the slot
+            if (act) {
+                pown = (i32)gs[lane].pad_[0];
+                if (type == ZT_MATCH) {
+                    ma = gs[lane].a; mb = gs[lane].b; mc = gs[lane].c; mlimit = gs[lane].limit; mcxt = gs[lane].cxt;
+                    mcur = ht[mlimit & (i32)(ht_len - 1)];
+                }
+            }
+            if (VMH) vm_prev = gr->pad_[0];
+            else { z.a = gr->a; z.b = gr->b; z.c = gr->c; z.d = gr->d; z.f = gr->f; z.pc = gr->pc; }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // (H in LDS, written above by all lanes, read by lane 0)
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        }
 
 #ifdef ZPQ_LANES_PROF
         u64 prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -560,6 +595,20 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
                    (unsigned long long)prof[0], (unsigned long long)prof[1], (unsigned long long)prof[2], (unsigned long long)prof[3],
                    (unsigned long long)prof[4], (unsigned long long)prof[5], (unsigned long long)prof[6]);
 #endif
+        if (KEEP) {                                               // hand the block's state to the next segment's launch
+            if (act) {
+                gs[lane].pad_[0] = (u32)pown;
+                if (type == ZT_MATCH) { gs[lane].a = ma; gs[lane].b = mb; gs[lane].c = mc; gs[lane].limit = mlimit; gs[lane].cxt = mcxt; }
+            }
+            if (lane == 0) {
+                if (VMH) gr->pad_[0] = vm_prev;
+                else { gr->a = z.a; gr->b = z.b; gr->c = z.c; gr->d = z.d; gr->f = z.f; gr->pc = z.pc; }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            if (h_in_lds && !VMH) for (u32 i = lane; i < M.hlen; i += 64) reinterpret_cast<u32 *>(slot + M.h_off)[i] = hl[i];
+        }
         const i32 st0 = __builtin_amdgcn_readlane(status, 0);
         if (lane == last) {
             i32 stt = st0;
@@ -574,6 +623,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
+        if (KEEP) break;                                          // one block per slot and launch
     }
 }
 
@@ -601,7 +651,7 @@ __device__ __forceinline__ i32 row_sum_all(i32 x, int rb)
 
 // VMH as in k_lanes: true = the shipped hash chain, evaluated in registers; false = any program, through the shared
 // interpreter on lane 0 of every ROW (four interpreters per wave walking the same program on their own blocks' bytes).
-template <bool DEC, bool VMH = true>
+template <bool DEC, bool KEEP = false, bool VMH = true>
 __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B, const LCfg cfg)
 {
     extern __shared__ __align__(16) u8 lds[];
@@ -635,7 +685,9 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
     const bool act = li < n;
     const int slot_id = (blockIdx.x * WAVES + wave) * RPW + row;
     const int nslots = B.nslots;
-    u8 *slot = B.slots + (u64)slot_id * M.slot_bytes;
+    // (KEEP: rows beyond the launch's blocks code nothing and do not read past the map)
+    const int slot_ix = KEEP ? (slot_id < B.nblocks ? B.slot_map[slot_id] : 0) : slot_id;
+    u8 *slot = B.slots + (u64)slot_ix * M.slot_bytes;
 
     const DComp &C = M.comp[act ? li : 0];
     const int type = act ? C.type : 0;
@@ -666,7 +718,7 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
     };
 
     for (int blk = slot_id; slot_id < nslots && blk < B.nblocks; blk += nslots) {
-        {   // Predictor.init + ZPAQL.clear: the row zeroes its slot, then fills the non-zero tables
+        if (!KEEP) {   // Predictor.init + ZPAQL.clear: the row zeroes its slot, then fills the non-zero tables
             uint4 *z4 = reinterpret_cast<uint4 *>(slot);
             const u64 n16 = M.zero_bytes / 16;
             const uint4 zero = make_uint4(0, 0, 0, 0);
@@ -719,6 +771,19 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
         if (DEC && li == last)
             for (int k = 0; k < 4; k++) { u32 c = 0; if (ipos < nin) c = src[ipos++]; code = (code << 8) | c; }
         const u32 total = DEC ? 0xFFFFFFFFu : nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u);
+        DCompScal *gs = reinterpret_cast<DCompScal *>(slot + M.scal_off);
+        DVmRegs *gr = reinterpret_cast<DVmRegs *>(slot + M.regs_off);
+        if (KEEP) {                                               // what the last segment's launch left in the slot (see k_lanes)
+            if (act) {
+                pown = (i32)gs[li].pad_[0];
+                if (type == ZT_MATCH) {
+                    ma = gs[li].a; mb = gs[li].b; mc = gs[li].c; mlimit = gs[li].limit; mcxt = gs[li].cxt;
+                    mcur = ht[mlimit & (i32)(ht_len - 1)];
+                }
+            }
+            if (VMH) vm_prev = gr->pad_[0];
+            else { z.a = gr->a; z.b = gr->b; z.c = gr->c; z.d = gr->d; z.f = gr->f; z.pc = gr->pc; }
+        }
 
         for (u32 bi = 0; bi < total; bi++) {
             u32 ch = 0;
@@ -1034,6 +1099,16 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
             }
             for (int sft = 24; sft >= 0; sft -= 8) { if (opos < cap) dst[opos] = (u8)(high >> sft); opos++; }
         }
+        if (KEEP) {                                               // hand the block's state to the next segment's launch
+            if (act) {
+                gs[li].pad_[0] = (u32)pown;
+                if (type == ZT_MATCH) { gs[li].a = ma; gs[li].b = mb; gs[li].c = mc; gs[li].limit = mlimit; gs[li].cxt = mcxt; }
+            }
+            if (li == 0) {
+                if (VMH) gr->pad_[0] = vm_prev;
+                else { gr->a = z.a; gr->b = z.b; gr->c = z.c; gr->d = z.d; gr->f = z.f; gr->pc = z.pc; }
+            }
+        }
         const i32 vm_st = VMH ? (i32)ZPQ_OK : rowget(vm_status, 0);   // (the interpreter's step cap: lane 0 of the row)
         if (li == last) {
             i32 stt = vm_st;
@@ -1048,6 +1123,38 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
+        if (KEEP) break;                                          // one block per slot and launch
+    }
+}
+
+// Predictor.init + ZPAQL.clear (predictor.v:325-470, zpaql.v:54-95) of every member of a block set in one launch, in the
+// form the KEEP kernels load: the slot zeroed, the ZF_CONST / ZF_PATTERN tables and the a16 tables filled, MATCH's
+// initial scalars (quirk Q17: sizebits / bufbits left in a / b).  One workgroup per slot.
+__global__ void __launch_bounds__(256) k_set_init(const DModel *Mp, const uint32_t *img, uint8_t *slots)
+{
+    const DModel &M = *Mp;
+    u8 *slot = slots + (u64)blockIdx.x * M.slot_bytes;
+    uint4 *z4 = reinterpret_cast<uint4 *>(slot);
+    const u64 n16 = M.zero_bytes / 16;
+    const uint4 zero = make_uint4(0, 0, 0, 0);
+    for (u64 i = threadIdx.x; i < n16; i += 256) z4[i] = zero;
+    __syncthreads();                                              // (a workgroup's own stores, in order, before the fills)
+    for (i32 ci = 0; ci < M.n; ci++) {
+        const DComp &c = M.comp[ci];
+        if (c.cm_len && c.cm_fill != ZF_ZERO) {
+            u32 *t = reinterpret_cast<u32 *>(slot + c.cm_off);
+            if (c.cm_fill == ZF_CONST) { for (u32 i = threadIdx.x; i < c.cm_len; i += 256) t[i] = c.cm_fill_val; }
+            else { const u32 *im = img + c.cm_fill_val; for (u32 i = threadIdx.x; i < c.cm_len; i += 256) t[i] = im[i % c.cm_pat_len]; }
+        }
+        if (c.a16_len && c.a16_fill) {
+            u16 *t = reinterpret_cast<u16 *>(slot + c.a16_off);
+            for (u32 i = threadIdx.x; i < c.a16_len; i += 256) t[i] = (u16)c.a16_fill;
+        }
+        if (c.type == ZT_MATCH && threadIdx.x == 0) {
+            DCompScal *gs = reinterpret_cast<DCompScal *>(slot + M.scal_off);
+            gs[ci].a = c.a;
+            gs[ci].b = c.b;
+        }
     }
 }
 
@@ -1094,7 +1201,7 @@ extern "C" int zpq_lanes_blocks_per_cu(const DModel *M)
     zpql::LCfg cfg;
     const bool rows = lanes_cfg(M, &cfg) && rows_ok(cfg);
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rows ? (cfg.vm_hashes > 0 ? (const void *)zpql::k_rows<false, true> : (const void *)zpql::k_rows<false, false>) : (const void *)zpql::k_lanes<false, false>,
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rows ? (cfg.vm_hashes > 0 ? (const void *)zpql::k_rows<false, false, true> : (const void *)zpql::k_rows<false, false, false>) : (const void *)zpql::k_lanes<false, false, false>,
                                                      64 * zpql::WAVES, zpql::LDS_TOTAL) != hipSuccess || nb < 1)
         nb = 2;
     return nb * zpql::WAVES * (rows ? zpql::RPW : 1);
@@ -1107,6 +1214,40 @@ extern "C" const char *zpq_lanes_kernel_name(const DModel *M, int decode)
     return rows ? (decode ? "k_rows<decode>" : "k_rows<encode>") : (decode ? "k_lanes<decode>" : "k_lanes<encode>");
 }
 
+// block sets: Predictor.init + ZPAQL.clear of nmembers slots (the KEEP launches below never initialise)
+extern "C" int zpq_launch_lanes_set_init(const DModel *d_model, const uint32_t *d_img, uint8_t *slots, int nmembers, hipStream_t stream)
+{
+    if (nmembers < 1) return ZPQ_E_INTERNAL;
+    hipLaunchKernelGGL(zpql::k_set_init, dim3(nmembers), dim3(256), 0, stream, d_model, d_img, slots);
+    return ZPQ_OK;
+}
+
+// block sets: one segment of B->nblocks members in one launch, block i on slot B->slot_map[i]
+extern "C" int zpq_launch_lanes_keep(const DBatch *B, const DModel *hostM, int decode, hipStream_t stream)
+{
+    zpql::LCfg cfg;
+    if (!lanes_cfg(hostM, &cfg) || B->nblocks < 1 || B->nslots != B->nblocks || !B->slot_map) return ZPQ_E_INTERNAL;   // (no identity map: the slots are the set's)
+    const bool rows = rows_ok(cfg), vmh = cfg.vm_hashes > 0;
+    const int per_wg = zpql::WAVES * (rows ? zpql::RPW : 1);
+    const dim3 g((B->nblocks + per_wg - 1) / per_wg), t(64 * zpql::WAVES);
+    if (rows) {
+        if (vmh) {
+            if (decode) hipLaunchKernelGGL((zpql::k_rows<true, true, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+            else hipLaunchKernelGGL((zpql::k_rows<false, true, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+        } else {
+            if (decode) hipLaunchKernelGGL((zpql::k_rows<true, true, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+            else hipLaunchKernelGGL((zpql::k_rows<false, true, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+        }
+    } else if (vmh) {
+        if (decode) hipLaunchKernelGGL((zpql::k_lanes<true, true, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+        else hipLaunchKernelGGL((zpql::k_lanes<false, true, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+    } else {
+        if (decode) hipLaunchKernelGGL((zpql::k_lanes<true, true, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+        else hipLaunchKernelGGL((zpql::k_lanes<false, true, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+    }
+    return ZPQ_OK;
+}
+
 extern "C" int zpq_launch_lanes(const DBatch *B, const DModel *hostM, int decode, int nslots, hipStream_t stream)
 {
     zpql::LCfg cfg;
@@ -1115,22 +1256,22 @@ extern "C" int zpq_launch_lanes(const DBatch *B, const DModel *hostM, int decode
         const int per_wg = zpql::WAVES * zpql::RPW;
         const dim3 g((nslots + per_wg - 1) / per_wg), t(64 * zpql::WAVES);
         if (cfg.vm_hashes > 0) {
-            if (decode) hipLaunchKernelGGL((zpql::k_rows<true, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
-            else hipLaunchKernelGGL((zpql::k_rows<false, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+            if (decode) hipLaunchKernelGGL((zpql::k_rows<true, false, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+            else hipLaunchKernelGGL((zpql::k_rows<false, false, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
         } else {
-            if (decode) hipLaunchKernelGGL((zpql::k_rows<true, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
-            else hipLaunchKernelGGL((zpql::k_rows<false, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+            if (decode) hipLaunchKernelGGL((zpql::k_rows<true, false, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+            else hipLaunchKernelGGL((zpql::k_rows<false, false, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
         }
         return ZPQ_OK;
     }
     const int grid = (nslots + zpql::WAVES - 1) / zpql::WAVES;
     const dim3 g(grid), t(64 * zpql::WAVES);
     if (cfg.vm_hashes > 0) {
-        if (decode) hipLaunchKernelGGL((zpql::k_lanes<true, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
-        else hipLaunchKernelGGL((zpql::k_lanes<false, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+        if (decode) hipLaunchKernelGGL((zpql::k_lanes<true, false, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+        else hipLaunchKernelGGL((zpql::k_lanes<false, false, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
     } else {
-        if (decode) hipLaunchKernelGGL((zpql::k_lanes<true, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
-        else hipLaunchKernelGGL((zpql::k_lanes<false, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+        if (decode) hipLaunchKernelGGL((zpql::k_lanes<true, false, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+        else hipLaunchKernelGGL((zpql::k_lanes<false, false, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
     }
     return ZPQ_OK;
 }
