@@ -278,12 +278,26 @@ int zpq_block_decode_segment(zpq_block *, const uint8_t *in, size_t n, uint32_t 
  *                         starts every segment with p[] = 0, which differs only for a component whose input index is not
  *                         below its own.  The environment variable ZPQ_SET_LANES=1 makes the request for every set the
  *                         process creates, ZPQ_SET_LANES=0 withdraws it (anything but a leading 0 / 1 decides nothing).
+ *   ZPQ_SET_PIPE          a request: run the ENCODE calls of a chain-model set on the wave-pipelined encoder (k_pipe, a state
+ *                         hand-over form of it) instead of the lane-per-component one (k_chain).  Honoured when
+ *                         zpq_blockset_pipe_applies(model): a chain model of one of the five shapes that encoder codes (an
+ *                         ICM and 1, 2 or 4 ISSEs, or 5 or 7 ISSEs and a MIX2, with the shipped context programs: levels
+ *                         1-5).  Otherwise it decides nothing.  The choice is made per call, as both encoders keep the same
+ *                         state in the set's slots: a call with fewer than 12 live members, or under ZPQ_ENC_PIPE=0, runs
+ *                         on the chain encoder, the next one may run on the pipeline again.  Decode calls and the set's
+ *                         capacity are those of the chain kernel.  The coded bytes are identical either way;
+ *                         zpq_ctx_last_kernel_name tells which ran ("k_pipe<encode>" / "k_chain<encode>").  The value is
+ *                         4: bit 1 is not a flag and stays refused.  ZPQ_SET_PIPE=1 in the environment makes the request
+ *                         for every set the process creates, ZPQ_SET_PIPE=0 withdraws it (same rule as ZPQ_SET_LANES).
+ *                         The two requests are resolved independently; no model can have both.
  *   zpq_blockset_flags    the ZPQ_SET_* in force for a set (0 for a request that decided nothing).  Like every call on a
  *                         set it must not race with zpq_blockset_destroy of the same handle.
- *   zpq_blockset_lanes_applies / zpq_blockset_resolve_flags   host logic only, no device needed: would the request be
- *                         honoured for this model; the flags a set created with `flags` would get (environment applied).
+ *   zpq_blockset_lanes_applies / zpq_blockset_pipe_applies / zpq_blockset_resolve_flags   host logic only, no device
+ *                         needed: would the request be honoured for this model (its shape alone, neither a batch size nor
+ *                         the environment); the flags a set created with `flags` would get (environment applied).
  */
 #define ZPQ_SET_LANES 1u
+#define ZPQ_SET_PIPE 4u
 typedef struct zpq_blockset zpq_blockset;
 int zpq_blockset_create(zpq_ctx *, const zpq_model *, int nmembers, uint64_t max_member_bytes, zpq_blockset **out);
 int zpq_blockset_create_ex(zpq_ctx *, const zpq_model *, int nmembers, uint64_t max_member_bytes, uint32_t flags, zpq_blockset **out);
@@ -292,6 +306,7 @@ int zpq_blockset_capacity(zpq_ctx *, const zpq_model *, uint64_t max_member_byte
 int zpq_blockset_capacity_ex(zpq_ctx *, const zpq_model *, uint64_t max_member_bytes, uint32_t flags);
 unsigned zpq_blockset_flags(const zpq_blockset *);
 int zpq_blockset_lanes_applies(const zpq_model *);
+int zpq_blockset_pipe_applies(const zpq_model *);
 int zpq_blockset_resolve_flags(const zpq_model *, uint32_t flags);
 int zpq_blockset_encode_segments(zpq_blockset *, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
                                  uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status);

@@ -1,8 +1,8 @@
 """Are the kernels two builds share the same code?  Disassembles every gfx950 code object of two libzpaq_hip.so builds
 (llvm-objdump, no GPU needed) and compares, per kernel symbol, the list of instructions with their operands.
     python tools/isa_identity.py OLD.so NEW.so [name filter ...]      (default filters: k_chain k_pipe)
-A k_chain symbol of OLD that NEW lacks is looked up with one more `false` template argument (a parameter added at the end
-with a default); a k_lanes / k_rows symbol with `false` in front of its last template argument (KEEP, added before VMH, which
+A k_chain or k_pipe symbol of OLD that NEW lacks is looked up with one more `false` template argument (a parameter added at
+the end with a default: KEEP); a k_lanes / k_rows symbol with `false` in front of its last template argument (KEEP, added before VMH, which
 stays last).  What follows a kernel's last s_endpgm is no code -- s_nop fill up to the next symbol's alignment, the
 prefetch guard behind the module's last function, objdump's `...` for a run of it -- and depends on which function comes
 next, so it is left out of the comparison.  Prints the kernels that differ with their per-opcode count changes, then the totals."""

@@ -32,6 +32,8 @@
 extern "C" void zpq_launch_generic(const DBatch *B, const DModel *hostM, int decode, int grid, hipStream_t stream);
 extern "C" int zpq_generic_blocks_per_cu(const DModel *M);
 extern "C" int zpq_lanes_supported(const DModel *M);
+extern "C" int zpq_pipe_shape_applies(const DModel *M);   // zpq_pipe.hip: the chain is one of the shapes k_pipe codes
+#define ZPQ_SET_ALL (ZPQ_SET_LANES | ZPQ_SET_PIPE)
 extern "C" int zpq_launch_lanes_set_init(const DModel *d_model, const uint32_t *d_img, uint8_t *slots, int nmembers, hipStream_t stream);
 extern "C" int zpq_launch_lanes_keep(const DBatch *B, const DModel *hostM, int decode, hipStream_t stream);
 extern "C" int zpq_lanes_blocks_per_cu(const DModel *M);
@@ -1233,13 +1235,24 @@ extern "C" int zpq_blockset_lanes_applies(const zpq_model *m) try
 {
     return m && !set_is_chain(m) && zpq_lanes_supported(&m->d) ? 1 : 0;
 } ZPQ_CATCH(return 0)
+// ZPQ_SET_PIPE, a request of the same kind: honoured where the wave-pipelined encoder codes the model's chain (its five
+// shapes); ZPQ_SET_PIPE=1 / =0 in the environment by the same rule.  No model can have both.
+extern "C" int zpq_blockset_pipe_applies(const zpq_model *m) try
+{
+    return m && set_is_chain(m) && zpq_pipe_shape_applies(&m->d) ? 1 : 0;
+} ZPQ_CATCH(return 0)
+static bool set_request(const char *var, uint32_t flags, uint32_t bit)
+{
+    const char *ev = getenv(var);
+    const bool env = ev && (ev[0] == '0' || ev[0] == '1');
+    return env ? ev[0] == '1' : (flags & bit) != 0;
+}
 extern "C" int zpq_blockset_resolve_flags(const zpq_model *m, uint32_t flags) try
 {
-    if (!m || (flags & ~(uint32_t)ZPQ_SET_LANES)) return ZPQ_E_ARG;
-    const char *ev = getenv("ZPQ_SET_LANES");
-    const bool env = ev && (ev[0] == '0' || ev[0] == '1');
-    const bool want = env ? ev[0] == '1' : (flags & ZPQ_SET_LANES) != 0;
-    return want && zpq_blockset_lanes_applies(m) ? (int)ZPQ_SET_LANES : 0;
+    if (!m || (flags & ~(uint32_t)ZPQ_SET_ALL)) return ZPQ_E_ARG;
+    const bool lanes = set_request("ZPQ_SET_LANES", flags, ZPQ_SET_LANES) && zpq_blockset_lanes_applies(m);
+    const bool pipe = set_request("ZPQ_SET_PIPE", flags, ZPQ_SET_PIPE) && zpq_blockset_pipe_applies(m);
+    return (int)((lanes ? ZPQ_SET_LANES : 0u) | (pipe ? ZPQ_SET_PIPE : 0u));
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 static int set_capacity(zpq_ctx *c, const DModel &layout, bool chain, bool lanes)
@@ -1255,7 +1268,7 @@ static int set_capacity(zpq_ctx *c, const DModel &layout, bool chain, bool lanes
 
 extern "C" int zpq_blockset_capacity_ex(zpq_ctx *c, const zpq_model *m, uint64_t max_member_bytes, uint32_t flags) try
 {
-    if (flags & ~(uint32_t)ZPQ_SET_LANES) return ZPQ_E_ARG;
+    if (flags & ~(uint32_t)ZPQ_SET_ALL) return ZPQ_E_ARG;
     if (!ctx_live(c)) return c ? ZPQ_E_CLOSED : ZPQ_E_ARG;
     if (!m) return ZPQ_E_ARG;
     HIPCK(hipSetDevice(c->device));
@@ -1263,7 +1276,9 @@ extern "C" int zpq_blockset_capacity_ex(zpq_ctx *c, const zpq_model *m, uint64_t
     static thread_local DModel layout;
     uint32_t sp = 0;
     const bool chain = set_layout(c, m, max_member_bytes, &layout, &sp);
-    return set_capacity(c, layout, chain, zpq_blockset_resolve_flags(m, flags) == (int)ZPQ_SET_LANES);
+    // (ZPQ_SET_PIPE changes nothing here: any round of such a set may fall back to the chain encoder)
+    const int rf = zpq_blockset_resolve_flags(m, flags);
+    return set_capacity(c, layout, chain, rf > 0 && ((uint32_t)rf & ZPQ_SET_LANES) != 0);
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 extern "C" int zpq_blockset_capacity(zpq_ctx *c, const zpq_model *m, uint64_t max_member_bytes) try
@@ -1275,7 +1290,7 @@ extern "C" int zpq_blockset_create_ex(zpq_ctx *c, const zpq_model *m, int nmembe
 {
     if (!out) return ZPQ_E_ARG;
     *out = nullptr;
-    if (flags & ~(uint32_t)ZPQ_SET_LANES) return ZPQ_E_ARG;
+    if (flags & ~(uint32_t)ZPQ_SET_ALL) return ZPQ_E_ARG;
     if (!ctx_live(c)) return c ? ZPQ_E_CLOSED : ZPQ_E_ARG;
     if (!m || nmembers < 1) return ZPQ_E_ARG;
     HIPCK(hipSetDevice(c->device));
@@ -1445,6 +1460,7 @@ static int set_segments(zpq_blockset *s, int decode, int n, const int32_t *membe
         B.squash = c->d_squash; B.stretch = c->d_stretch; B.dt = c->d_dt; B.dt2k = c->d_dt2k;
         B.ns = c->d_ns; B.stretch_c = c->d_stretch_c;
         B.slot_map = (const int32_t *)c->s_misc.p;
+        if (!decode && (s->flags & ZPQ_SET_PIPE)) B.flags |= ZB_SET_PIPE;   // this call may run on k_pipe<..., KEEP> (zpq_launch_chain)
         c->last_slots = k;
         c->last_sp = s->sp;
         if (s->chain) {

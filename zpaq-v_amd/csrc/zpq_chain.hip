@@ -1678,9 +1678,13 @@ extern "C" int zpq_launch_chain(const DBatch *B, const DModel *hostM, int decode
     if (blocks_per_wg < 64 / cfg.g || blocks_per_wg > cfg.blocks_per_wg || blocks_per_wg % (64 / cfg.g)) return ZPQ_E_INTERNAL;
     if (name_out) *name_out = decode ? "k_chain<decode>" : "k_chain<encode>";
     // a block set's launch (state hand-over through the slots): k_chain<..., KEEP> in both directions, whatever the batch
-    // planner would pick for independent blocks -- the pipe kernels keep no state
+    // planner would pick for independent blocks -- or, for an encode call of a set that asked for it (ZB_SET_PIPE) and has
+    // the pipeline's floor of members, k_pipe<..., KEEP>: the two keep the same state format, so the choice is per call
     const bool keep = (B->flags & ZB_KEEP_STATE) != 0;
     if (keep && (hio || B->nslots < B->nblocks)) return ZPQ_E_INTERNAL;   // one block per slot and launch
+    if (keep && !decode && (B->flags & ZB_SET_PIPE) && B->slot_map && zpq_pipe_applies(hostM, blocks_per_wg, B->nslots)) {
+        return zpq_launch_pipe(B, hostM, nwg, blocks_per_wg, stream, name_out);   // "k_pipe<encode>"
+    }
     if (!keep && !decode && zpq_pipe_applies(hostM, blocks_per_wg, B->nslots)) {
         return zpq_launch_pipe(B, hostM, nwg, blocks_per_wg, stream, name_out);   // "k_pipe<encode>" or "k_pipe2<encode>" (split stages)
     }

@@ -135,7 +135,8 @@ struct Row {
 // ------------------------------------------------------------------ a component stage
 // IS_LAST: the component the coder follows (its link carries squash(p) and the bit).  FWD_PIN: the last ISSE of a chain
 // that a MIX2 follows: it hands its INPUT on as well (the MIX2 mixes p[n-3] and p[n-2], levels.v:199-218,290-375).
-template <int NCH, bool SP, bool HIO, bool IS_ICM, bool IS_LAST, bool FWD_PIN>
+// KEEP: the block goes on from the state an earlier launch left in its slot and leaves its own there (k_pipe).
+template <int NCH, bool SP, bool HIO, bool IS_ICM, bool IS_LAST, bool FWD_PIN, bool KEEP = false>
 __device__ __forceinline__ void comp_loop(const StageArgs &S)
 {
     const DBatch &B = *S.B;
@@ -186,6 +187,18 @@ __device__ __forceinline__ void comp_loop(const StageArgs &S)
     bool sp_full = false;
     u32 sp_claims = 0;
     const u32 sp_limit = sp_cap - (sp_cap >> 4);
+    if constexpr (KEEP) {
+        // the hash program's registers, and the store's claim count and full flag, where k_chain<..., KEEP> keeps them
+        // (Every stage reads the same two words, and the ICM's wave writes them behind its byte loop: a stage has used its
+        //  copy by the barrier that ends its first byte, which the ICM's last barrier never precedes.)
+        const DVmRegs *kregs = reinterpret_cast<const DVmRegs *>(slot + M.regs_off);
+        if (NCH == 2) { m4 = kregs->pad_[0]; b4 = kregs->pad_[1]; }
+        else prev = kregs->pad_[0];
+        if constexpr (SP) {
+            const DCompScal *kscal = reinterpret_cast<const DCompScal *>(slot + M.scal_off) + ci;
+            sp_claims = (u32)kscal->a; sp_full = kscal->b != 0;
+        }
+    }
 
 #ifdef ZPP_DEBUG_NO_ROWS   // timing experiment only (wrong output): no hash-row traffic
 #define ZPP_LOAD_ROWS(q_, po_) do { q_.A = u32x4{(po_), 0, 0, 0}; q_.B = q_.A; q_.C = q_.A; } while (0)
@@ -472,6 +485,23 @@ __device__ __forceinline__ void comp_loop(const StageArgs &S)
     if (HIO && phase == 0 && B.gate_flag && !gate_wait(B.gate_flag)) status = ZPQ_E_INTERNAL;
     }   // phase
     // (the last nibbles' rows are not written back: the slot is re-initialised for the next block)
+    if constexpr (KEEP) {
+        // ... unless the block goes on in a later launch.  The byte's first nibble was stored when its second was consumed
+        // (consume stores its L1, have1 = true there), so only the second one is still in registers -- under FWD2 too: the
+        // longer request distance changes what is forwarded from registers, not when a finished row is stored.
+        if (S.active) {
+            if (total) *reinterpret_cast<u32x4 *>(tbase + rowB.off) = u32x4{rowB.x, rowB.y, rowB.z, rowB.w};
+            if (IS_ICM) {                                  // one wave writes the registers every stage started from
+                DVmRegs *const kregs = reinterpret_cast<DVmRegs *>(slot + M.regs_off);
+                kregs->pad_[0] = NCH == 2 ? m4 : prev;
+                if (NCH == 2) kregs->pad_[1] = b4;         // (the hash chain has no use for b4: the word stays as it is)
+            }
+            if constexpr (SP) {
+                DCompScal *const kscal = reinterpret_cast<DCompScal *>(slot + M.scal_off) + ci;
+                kscal->a = (i32)sp_claims; kscal->b = sp_full ? 1 : 0;
+            }
+        }
+    }
     if (S.lane < S.bpw) reinterpret_cast<i32 *>(lds + S.L.stat_off)[ci * S.bpw + S.lane] = status;
 #undef ZPP_LOAD_ROWS
 }
@@ -770,7 +800,7 @@ __device__ __forceinline__ void pred_loop(const StageArgs &S, const int delay)
 // of a byte are eight DISTINCT entries, known when the byte begins: they are loaded there (after the previous byte's
 // trained weights are stored: an entry may recur), trained in registers, stored when the next byte begins.  The wait
 // for the loads is this wave's own; its SIMD is shared with component waves that keep issuing.
-template <int NCH, bool HIO>
+template <int NCH, bool HIO, bool KEEP = false>
 __device__ __forceinline__ void mix_loop(const StageArgs &S)
 {
     const DBatch &B = *S.B;
@@ -789,6 +819,16 @@ __device__ __forceinline__ void mix_loop(const StageArgs &S)
     InWin W;
     if (S.active) W.open(S.src, S.nin, B.in_off);
     u32 prev = 0, hctx = 0, mh_prev = 0, mch_prev = 0;
+    if constexpr (KEEP) {
+        prev = reinterpret_cast<const DVmRegs *>(S.slot + M.regs_off)->pad_[0];   // (comp_loop)
+        // (This stage's status word now -- nobody looks at it before the loops are over -- and its address computed HERE: hoisted
+        //  in front of the branch between the stages it is one register more than level 5's dense chain has, and is spilled.
+        //  The empty asm only pins the computation to this place; tests/test_kernel_resources.py (zero scratch in every k_pipe
+        //  instantiation) is what tells when a compiler update undoes it.)
+        u32 sl = (u32)S.lane;
+        asm volatile("; the status word's address is computed in this stage" : "+v"(sl));
+        if (sl < (u32)S.bpw) reinterpret_cast<i32 *>(lds + S.L.stat_off)[(u32)(NCH * S.bpw) + sl] = ZPQ_OK;
+    }
     u32 mw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     u32 it = 0;
     for (int phase = 0; phase < (HIO ? 2 : 1); phase++) {
@@ -844,7 +884,14 @@ __device__ __forceinline__ void mix_loop(const StageArgs &S)
     if (HIO && phase == 0 && B.gate_flag) (void)gate_wait(B.gate_flag);
     }   // phase
     // (the last byte's weights are not written back: the slot is re-initialised for the next block)
-    if (S.lane < S.bpw) reinterpret_cast<i32 *>(lds + S.L.stat_off)[NCH * S.bpw + S.lane] = ZPQ_OK;
+    if constexpr (KEEP) {
+        // ... unless the block goes on in a later launch
+        if (S.active && total) {
+#pragma unroll
+            for (int t = 0; t < 8; t++) a16[(mh_prev + ((1u << t) | (mch_prev >> (8 - t)))) & cmask] = (u16)mw[t];
+        }
+    }
+    if (!KEEP && S.lane < S.bpw) reinterpret_cast<i32 *>(lds + S.L.stat_off)[NCH * S.bpw + S.lane] = ZPQ_OK;
 }
 
 // ------------------------------------------------------------------ the coder stage (encoder.v:48-139)
@@ -908,9 +955,16 @@ template <int NST, bool HIO>
 __device__ __forceinline__ void coder_loop(const StageArgs &S, Coder &X) { coder_loop_d<NST, HIO>(S, X, NST); }
 
 // NCH = chain length (ICM + ISSEs), MIXT = a MIX2 follows it (levels 4-5); waves: NCH [+ 1] + the coder
-template <int NCH, bool MIXT, bool SP, bool HIO>
+// KEEP = state hand-over between launches (block sets), in the slot format of k_chain<..., KEEP> (zpq_chain.hip): any round of
+// a set may run on either encoder, and k_chain<decode, KEEP> decodes every one.  Lane l of workgroup w works on slot
+// slot_map[w * blocks_per_wg + l], one block per slot and launch.  Load: counters and weights from the slot's cm areas into
+// the LDS packing, prev / m4, b4 and the stores' claim counts into the stages; hash tables, tags, lines and the MIX2's weights
+// are used where they are.  Save: all of that back, with the rows and weights still in registers.  c8, hmap4, the context
+// hashes and the coder start again with every segment (predictor.v:827-833, compressor.v:238-245).  The byte loop is the same code.
+template <int NCH, bool MIXT, bool SP, bool HIO, bool KEEP = false>
 __global__ void __launch_bounds__(64 * (NCH + (MIXT ? 2 : 1))) k_pipe(const DBatch B, const Cfg cfg, const PipeLds L)
 {
+    static_assert(!(KEEP && HIO), "block sets take no part in striped transfers");
     extern __shared__ __align__(16) u8 lds[];
     const DModel &M = *B.model;
     const int tid = threadIdx.x, nthr = blockDim.x;
@@ -930,7 +984,12 @@ __global__ void __launch_bounds__(64 * (NCH + (MIXT ? 2 : 1))) k_pipe(const DBat
     const int nslots = B.nslots;
     const int slot_id = wg_slot0 + lane;
     const bool lane_on = lane < bpw && slot_id < nslots;
-    u8 *const slot = B.slots + (u64)(lane_on ? slot_id : wg_slot0) * M.slot_bytes;
+    u8 *slot = B.slots + (u64)(lane_on ? slot_id : wg_slot0) * M.slot_bytes;
+    if constexpr (KEEP) {
+        // (lanes beyond the batch code nothing; they only must not read past the map)
+        const int mi = lane_on ? slot_id : (wg_slot0 < nslots ? wg_slot0 : 0);
+        slot = B.slots + (u64)B.slot_map[mi] * M.slot_bytes;
+    }
     u8 *const my = lds + LDS_STATE + (lane_on ? lane : 0) * cfg.lds_per_block;
     u32 *const misc = reinterpret_cast<u32 *>(lds + L.misc_off);
     const int wg_slots = min(bpw, nslots - wg_slot0);                  // slots this workgroup owns (> 0)
@@ -940,7 +999,30 @@ __global__ void __launch_bounds__(64 * (NCH + (MIXT ? 2 : 1))) k_pipe(const DBat
         const bool active = lane_on && blk < B.nblocks;
         const int nact = min(wg_slots, B.nblocks - base);               // active slots are the first nact of the workgroup
         // ---- Predictor.init + ZPAQL.clear for the round's blocks (predictor.v:325-470, zpaql.v:54-95)
-        {
+        if constexpr (KEEP) {
+            // ... or the state an earlier launch left in the slots: counters and weights back into their LDS packing, the
+            // ICM's stretch rebuilt (zpq_chain.hip, the KEEP load)
+            for (int idx = tid; idx < nact * 256; idx += nthr) {
+                const int b = idx >> 8, i = idx & 255;
+                u8 *blk_lds = lds + LDS_STATE + b * cfg.lds_per_block;
+                const u8 *bslot = B.slots + (u64)B.slot_map[wg_slot0 + b] * M.slot_bytes;
+                {
+                    const u32 cmi = reinterpret_cast<const u32 *>(bslot + M.comp[0].cm_off)[i] & 0x7FFFFFu;
+                    const u32 wv = s_stretch[(cmi >> 12) & 2047u];
+                    const i32 sti = ((i32)wv >> 16) + (i32)__popc(__builtin_amdgcn_ubfe(wv, 1u, (cmi >> 8) & 15u));
+                    reinterpret_cast<u32 *>(blk_lds + cfg.lds_off32[0])[i] = cmi | (((u32)sti & 0x1FFu) << 23);
+                    (blk_lds + cfg.lds_off8[0])[i] = (u8)(sti >> 9);
+                }
+#pragma unroll 1
+                for (int c = 1; c < NCH; c++) {
+                    const u32 *cmk = reinterpret_cast<const u32 *>(bslot + M.comp[c].cm_off);
+                    const u32 a0 = cmk[2 * i], a1 = cmk[2 * i + 1];
+                    reinterpret_cast<u32 *>(blk_lds + cfg.lds_off32[c])[i] = (a0 & 0xFFFFFu) | (a1 << 20);
+                    (blk_lds + cfg.lds_off8[c])[i] = (u8)((i32)a1 >> 12);
+                }
+            }
+            if (tid == 0) *misc = 0u;
+        } else {
             const u64 n16 = M.zero_bytes / 16;
             const uint4 zero = make_uint4(0, 0, 0, 0);
             for (int b = 0; b < nact; b++) {
@@ -998,12 +1080,28 @@ __global__ void __launch_bounds__(64 * (NCH + (MIXT ? 2 : 1))) k_pipe(const DBat
 
         Coder X;
         X.low = 1; X.high = 0xFFFFFFFFu; X.opos = 0; X.cap = S.cap; X.dst = S.dst;
-        if (wave == 0) comp_loop<NCH, SP, HIO, true, false, false>(S);
-        else if (wave < NCH - 1) comp_loop<NCH, SP, HIO, false, false, false>(S);
-        else if (wave == NCH - 1) comp_loop<NCH, SP, HIO, false, !MIXT, MIXT>(S);
-        else if (MIXT && wave == NCH) mix_loop<NCH, HIO>(S);
+        if (wave == 0) comp_loop<NCH, SP, HIO, true, false, false, KEEP>(S);
+        else if (wave < NCH - 1) comp_loop<NCH, SP, HIO, false, false, false, KEEP>(S);
+        else if (wave == NCH - 1) comp_loop<NCH, SP, HIO, false, !MIXT, MIXT, KEEP>(S);
+        else if (MIXT && wave == NCH) mix_loop<NCH, HIO, KEEP>(S);
         else coder_loop<NST, HIO>(S, X);
         __syncthreads();
+        if constexpr (KEEP) {
+            // the LDS tables back into the slots' cm areas (the inverse packing; zpq_chain.hip, the KEEP save)
+            for (int idx = tid; idx < nact * 256; idx += nthr) {
+                const int b = idx >> 8, i = idx & 255;
+                const u8 *blk_lds = lds + LDS_STATE + b * cfg.lds_per_block;
+                u8 *bslot = B.slots + (u64)B.slot_map[wg_slot0 + b] * M.slot_bytes;
+                reinterpret_cast<u32 *>(bslot + M.comp[0].cm_off)[i] = reinterpret_cast<const u32 *>(blk_lds + cfg.lds_off32[0])[i] & 0x7FFFFFu;
+#pragma unroll 1
+                for (int c = 1; c < NCH; c++) {
+                    const u32 v = reinterpret_cast<const u32 *>(blk_lds + cfg.lds_off32[c])[i];
+                    u32 *cmk = reinterpret_cast<u32 *>(bslot + M.comp[c].cm_off);
+                    cmk[2 * i] = (u32)(((i32)(v << 12)) >> 12);
+                    cmk[2 * i + 1] = ((u32)(i32)(int8_t)(blk_lds + cfg.lds_off8[c])[i] << 12) | (v >> 20);
+                }
+            }
+        }
         if (wave == NST && active) {
             // ---- segment end: compress(-1) + flush (encoder.v:101-105,130-139)
             X.high = X.low;                                           // encode(1, 0): mid = low, high = mid
@@ -1178,6 +1276,19 @@ static bool pipe_layout(const Cfg &cfg, int bpw, zpqp::PipeLds *L, size_t *lds_b
 // The wave-pipelined encoder exists for the dense and line-store chains of levels 1-5.  ZPQ_ENC_PIPE=0 keeps the
 // lane-per-component encoder (tests compare the two).
 // (a batch of fewer than 12 resident blocks stays with the lane-per-component encoder: see zpq_launch_pipe)
+// the five shapes k_pipe codes: a chain of 2, 3 or 5 components, or one of 6 or 8 with a MIX2 behind it
+static bool pipe_shape(const Cfg &cfg)
+{
+    return cfg.has_mix2 ? (cfg.nch_spec == 6 || cfg.nch_spec == 8) : (cfg.nch_spec == 2 || cfg.nch_spec == 3 || cfg.nch_spec == 5);
+}
+
+// (the model's shape alone: neither the batch size nor the environment; zpq_blockset_pipe_applies)
+extern "C" int zpq_pipe_shape_applies(const DModel *M)
+{
+    Cfg cfg;
+    return M && zpq_chain_build_cfg(M, &cfg) && pipe_shape(cfg) ? 1 : 0;
+}
+
 extern "C" int zpq_pipe_applies(const DModel *M, int blocks_per_wg, int nslots)
 {
     if (nslots < 12) return 0;
@@ -1185,7 +1296,7 @@ extern "C" int zpq_pipe_applies(const DModel *M, int blocks_per_wg, int nslots)
     if (ev && atoi(ev) == 0) return 0;
     Cfg cfg;
     if (!zpq_chain_build_cfg(M, &cfg)) return 0;
-    if (cfg.has_mix2 ? !(cfg.nch_spec == 6 || cfg.nch_spec == 8) : !(cfg.nch_spec == 2 || cfg.nch_spec == 3 || cfg.nch_spec == 5)) return 0;
+    if (!pipe_shape(cfg)) return 0;
     if (blocks_per_wg < 1 || blocks_per_wg > 64 || blocks_per_wg > cfg.blocks_per_wg) return 0;
     zpqp::PipeLds L;
     size_t lds = 0;
@@ -1241,6 +1352,9 @@ extern "C" int zpq_launch_pipe(const DBatch *B, const DModel *hostM, int nwg, in
     }
     const bool hio = B->gate_flag != nullptr;
     if (hio && cfg.sparse) return ZPQ_E_INTERNAL;            // (striped uploads: dense levels 1-2, see zpq_chain_has_hio)
+    // a block set's launch (ZPQ_SET_PIPE): k_pipe<..., KEEP>, block i on slot slot_map[i], one block per slot and launch
+    const bool keep = (B->flags & ZB_KEEP_STATE) != 0;
+    if (keep && (hio || !B->slot_map || B->nslots != B->nblocks)) return ZPQ_E_INTERNAL;
     // Dense level 1: every stage split into a history wave and a counter / weights wave (k_pipe2): 136 -> 101 ms for 4096
     // blocks.  Level 2 has seven such roles for four SIMDs; every order and every mix of split and whole stages that was
     // tried ran at 122-137 ms against 123 for k_pipe (two waves sharing a SIMD issue slower together than the instruction
@@ -1250,7 +1364,8 @@ extern "C" int zpq_launch_pipe(const DBatch *B, const DModel *hostM, int nwg, in
     {
         const char *ev = getenv("ZPQ_ENC_SPLIT");
         cfg.split_enc = 0;
-        if (!cfg.sparse && !cfg.has_mix2 && (cfg.nch_spec == 2 || cfg.nch_spec == 3) && !(ev && atoi(ev) == 0 && strlen(ev) == 1)) {
+        // (k_pipe2 has no KEEP form: a set's dense short chain runs on unsplit k_pipe, whatever ZPQ_ENC_SPLIT says)
+        if (!keep && !cfg.sparse && !cfg.has_mix2 && (cfg.nch_spec == 2 || cfg.nch_spec == 3) && !(ev && atoi(ev) == 0 && strlen(ev) == 1)) {
             // (level 2, round 4: both ISSEs on the two halves of one wave, "60cd1" -- five roles as at level 1 -- takes the floor
             //  without row traffic from 113.7 to 84.8 ms, but with the rows it runs at the memory system's rate for random lines
             //  read and written back: 119.4 / 123.7-133 / 126.3 ms against 122.7 / 121-131 / 123.7 for k_pipe on three boxes.
@@ -1282,11 +1397,12 @@ extern "C" int zpq_launch_pipe(const DBatch *B, const DModel *hostM, int nwg, in
     // would then share SIMDs while other CUs idle (measured: 1024 blocks 254 ms instead of 114).  Asking for more than
     // half of the LDS keeps it at one workgroup per CU, one wave per SIMD.
     { const char *ev = getenv("ZPQ_PIPE_SHARE"); if (!(ev && atoi(ev) == 1) && lds < 81 * 1024) lds = 81 * 1024; }
-#define ZPP_LAUNCH(N, MX, SPv, HIOv)                                                                                 \
+#define ZPP_LAUNCH_K(N, MX, SPv, HIOv, KP)                                                                           \
     do {                                                                                                             \
-        (void)hipFuncSetAttribute((const void *)zpqp::k_pipe<N, MX, SPv, HIOv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        hipLaunchKernelGGL((zpqp::k_pipe<N, MX, SPv, HIOv>), dim3(nwg), dim3(64 * ((N) + ((MX) ? 2 : 1))), lds, stream, *B, cfg, L); \
+        (void)hipFuncSetAttribute((const void *)zpqp::k_pipe<N, MX, SPv, HIOv, KP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+        hipLaunchKernelGGL((zpqp::k_pipe<N, MX, SPv, HIOv, KP>), dim3(nwg), dim3(64 * ((N) + ((MX) ? 2 : 1))), lds, stream, *B, cfg, L); \
     } while (0)
+#define ZPP_LAUNCH(N, MX, SPv, HIOv) ZPP_LAUNCH_K(N, MX, SPv, HIOv, false)
     if (hio && !(cfg.nch_spec == 2 || cfg.nch_spec == 3)) return ZPQ_E_INTERNAL;
 #define ZPP_LAUNCH2(N, HIOv)                                                                                         \
     do {                                                                                                             \
@@ -1300,6 +1416,17 @@ extern "C" int zpq_launch_pipe(const DBatch *B, const DModel *hostM, int nwg, in
         return ZPQ_OK;
     }
 #undef ZPP_LAUNCH2
+    if (keep) {
+        switch (cfg.nch_spec) {
+        case 2: if (cfg.sparse) ZPP_LAUNCH_K(2, false, true, false, true); else ZPP_LAUNCH_K(2, false, false, false, true); break;
+        case 3: if (cfg.sparse) ZPP_LAUNCH_K(3, false, true, false, true); else ZPP_LAUNCH_K(3, false, false, false, true); break;
+        case 5: if (cfg.sparse) ZPP_LAUNCH_K(5, false, true, false, true); else ZPP_LAUNCH_K(5, false, false, false, true); break;
+        case 6: if (cfg.sparse) ZPP_LAUNCH_K(6, true, true, false, true); else ZPP_LAUNCH_K(6, true, false, false, true); break;
+        case 8: if (cfg.sparse) ZPP_LAUNCH_K(8, true, true, false, true); else ZPP_LAUNCH_K(8, true, false, false, true); break;
+        default: return ZPQ_E_INTERNAL;
+        }
+        return ZPQ_OK;
+    }
     switch (cfg.nch_spec) {
     case 2: if (cfg.sparse) ZPP_LAUNCH(2, false, true, false); else if (hio) ZPP_LAUNCH(2, false, false, true); else ZPP_LAUNCH(2, false, false, false); break;
     case 3: if (cfg.sparse) ZPP_LAUNCH(3, false, true, false); else if (hio) ZPP_LAUNCH(3, false, false, true); else ZPP_LAUNCH(3, false, false, false); break;
@@ -1309,5 +1436,6 @@ extern "C" int zpq_launch_pipe(const DBatch *B, const DModel *hostM, int nwg, in
     default: return ZPQ_E_INTERNAL;
     }
 #undef ZPP_LAUNCH
+#undef ZPP_LAUNCH_K
     return ZPQ_OK;
 }
