@@ -290,14 +290,32 @@ int zpq_block_decode_segment(zpq_block *, const uint8_t *in, size_t n, uint32_t 
  *                         4: bit 1 is not a flag and stays refused.  ZPQ_SET_PIPE=1 in the environment makes the request
  *                         for every set the process creates, ZPQ_SET_PIPE=0 withdraws it (same rule as ZPQ_SET_LANES).
  *                         The two requests are resolved independently; no model can have both.
+ *   ZPQ_SET_WAVES         a request on top of ZPQ_SET_LANES: run the calls of such a set on the wave-per-component kernels
+ *                         (k_gpipe / k_gdec's state hand-over forms, k_wset / k_wsetd: a wave is a component, a lane a
+ *                         member).  Honoured where ZPQ_SET_LANES is in force for the set (flag or environment, and honoured)
+ *                         and zpq_blockset_waves_applies(model): the lanes predicate, and the model is one both wave kernels
+ *                         take -- every input an earlier component, a MIX of at most 8 inputs, the shipped hash chain as
+ *                         HCOMP, the rings and the decoder's LDS within 160 KiB (its shape alone; ZPQ_ENC_GPIPE /
+ *                         ZPQ_DEC_GPIPE do not enter it).  Otherwise it decides nothing: alone on a general model it resolves
+ *                         to 0, on a chain model to what the other bits give.  A honoured set reports ZPQ_SET_LANES |
+ *                         ZPQ_SET_WAVES (17).  The choice is made per call, the slots hold one format for both families: an
+ *                         encode call under ZPQ_ENC_GPIPE=0, a decode call under ZPQ_DEC_GPIPE=0 (read at the call) runs on
+ *                         k_rows / k_lanes as without the request (ZPQ_LANES_ROWS chooses between those), the next call may
+ *                         run on the wave kernels again.  No floor on the number of members.  ZPQ_GPIPE_BATCH=0 selects the
+ *                         bit-serial encoder stages as for plain batches; ZPQ_GDEC_BPW is ignored (always 64 lanes per
+ *                         workgroup).  Same coded bytes whichever kernel ran; zpq_ctx_last_kernel_name tells which
+ *                         ("k_wset<encode>" / "k_wsetd<decode>").  The capacity stays that of ZPQ_SET_LANES: memory alone.
+ *                         ZPQ_SET_WAVES=1 / =0 in the environment by the rule of ZPQ_SET_LANES, resolved on its own and then
+ *                         combined: a process that wants it from the environment sets both variables.
  *   zpq_blockset_flags    the ZPQ_SET_* in force for a set (0 for a request that decided nothing).  Like every call on a
  *                         set it must not race with zpq_blockset_destroy of the same handle.
- *   zpq_blockset_lanes_applies / zpq_blockset_pipe_applies / zpq_blockset_resolve_flags   host logic only, no device
+ *   zpq_blockset_lanes_applies / _pipe_applies / _waves_applies / zpq_blockset_resolve_flags   host logic only, no device
  *                         needed: would the request be honoured for this model (its shape alone, neither a batch size nor
  *                         the environment); the flags a set created with `flags` would get (environment applied).
  */
 #define ZPQ_SET_LANES 1u
 #define ZPQ_SET_PIPE 4u
+#define ZPQ_SET_WAVES 16u
 typedef struct zpq_blockset zpq_blockset;
 int zpq_blockset_create(zpq_ctx *, const zpq_model *, int nmembers, uint64_t max_member_bytes, zpq_blockset **out);
 int zpq_blockset_create_ex(zpq_ctx *, const zpq_model *, int nmembers, uint64_t max_member_bytes, uint32_t flags, zpq_blockset **out);
@@ -307,6 +325,7 @@ int zpq_blockset_capacity_ex(zpq_ctx *, const zpq_model *, uint64_t max_member_b
 unsigned zpq_blockset_flags(const zpq_blockset *);
 int zpq_blockset_lanes_applies(const zpq_model *);
 int zpq_blockset_pipe_applies(const zpq_model *);
+int zpq_blockset_waves_applies(const zpq_model *);
 int zpq_blockset_resolve_flags(const zpq_model *, uint32_t flags);
 int zpq_blockset_encode_segments(zpq_blockset *, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
                                  uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status);

@@ -33,9 +33,12 @@ extern "C" void zpq_launch_generic(const DBatch *B, const DModel *hostM, int dec
 extern "C" int zpq_generic_blocks_per_cu(const DModel *M);
 extern "C" int zpq_lanes_supported(const DModel *M);
 extern "C" int zpq_pipe_shape_applies(const DModel *M);   // zpq_pipe.hip: the chain is one of the shapes k_pipe codes
-#define ZPQ_SET_ALL (ZPQ_SET_LANES | ZPQ_SET_PIPE)
+#define ZPQ_SET_ALL (ZPQ_SET_LANES | ZPQ_SET_PIPE | ZPQ_SET_WAVES)
 extern "C" int zpq_launch_lanes_set_init(const DModel *d_model, const uint32_t *d_img, uint8_t *slots, int nmembers, hipStream_t stream);
 extern "C" int zpq_launch_lanes_keep(const DBatch *B, const DModel *hostM, int decode, hipStream_t stream);
+extern "C" int zpq_launch_wset(const DBatch *B, const DModel *hostM, int decode, hipStream_t stream, const char **name);   // ZPQ_SET_WAVES: k_wset / k_wsetd
+extern "C" int zpq_gpipe_shape_applies(const DModel *M);        // the envelopes of the wave kernels from the model's shape alone
+extern "C" int zpq_gdec_shape_applies(const DModel *M);
 extern "C" int zpq_lanes_blocks_per_cu(const DModel *M);
 extern "C" int zpq_launch_lanes(const DBatch *B, const DModel *hostM, int decode, int nslots, hipStream_t stream);
 extern "C" const char *zpq_lanes_kernel_name(const DModel *M, int decode);   // k_rows (four blocks per wave) or k_lanes
@@ -201,7 +204,8 @@ struct zpq_block {
 // N blocks whose model state persists across segments, coded a segment of each per launch (zpq_blockset_*).  The state
 // lives in the set's own slots, in the layout chosen when the set is made: chain models on k_chain<..., KEEP> (dense tables
 // or the line store, sized by max_member_bytes), every other model on k_generic with ZB_KEEP_STATE, a launch per member --
-// or, on request (ZPQ_SET_LANES) and with at most 64 components, on the KEEP forms of k_rows / k_lanes, a launch per round.
+// or, on request (ZPQ_SET_LANES) and with at most 64 components, on the KEEP forms of k_rows / k_lanes, a launch per round;
+// with ZPQ_SET_WAVES on top, and a model both wave-per-component kernels take, on k_wset / k_wsetd (zpq_gpipe.hip), call by call.
 struct zpq_blockset {
     zpq_ctx *ctx = nullptr;        // nullptr once the ctx has been destroyed (orphaned set)
     const zpq_model *model = nullptr;   // the set holds a reference
@@ -1241,6 +1245,13 @@ extern "C" int zpq_blockset_pipe_applies(const zpq_model *m) try
 {
     return m && set_is_chain(m) && zpq_pipe_shape_applies(&m->d) ? 1 : 0;
 } ZPQ_CATCH(return 0)
+// ZPQ_SET_WAVES, a request on top of ZPQ_SET_LANES: honoured where that one is in force for the set and both wave-per-component
+// kernels take the model (gpipe_cfg: the shape alone; ZPQ_ENC_GPIPE / ZPQ_DEC_GPIPE choose the kernel per call, not here).
+// ZPQ_SET_WAVES=1 / =0 in the environment by the same rule, resolved on its own and then combined.
+extern "C" int zpq_blockset_waves_applies(const zpq_model *m) try
+{
+    return zpq_blockset_lanes_applies(m) && zpq_gpipe_shape_applies(&m->d) && zpq_gdec_shape_applies(&m->d) ? 1 : 0;
+} ZPQ_CATCH(return 0)
 static bool set_request(const char *var, uint32_t flags, uint32_t bit)
 {
     const char *ev = getenv(var);
@@ -1252,7 +1263,8 @@ extern "C" int zpq_blockset_resolve_flags(const zpq_model *m, uint32_t flags) tr
     if (!m || (flags & ~(uint32_t)ZPQ_SET_ALL)) return ZPQ_E_ARG;
     const bool lanes = set_request("ZPQ_SET_LANES", flags, ZPQ_SET_LANES) && zpq_blockset_lanes_applies(m);
     const bool pipe = set_request("ZPQ_SET_PIPE", flags, ZPQ_SET_PIPE) && zpq_blockset_pipe_applies(m);
-    return (int)((lanes ? ZPQ_SET_LANES : 0u) | (pipe ? ZPQ_SET_PIPE : 0u));
+    const bool waves = lanes && set_request("ZPQ_SET_WAVES", flags, ZPQ_SET_WAVES) && zpq_blockset_waves_applies(m);
+    return (int)((lanes ? ZPQ_SET_LANES : 0u) | (pipe ? ZPQ_SET_PIPE : 0u) | (waves ? ZPQ_SET_WAVES : 0u));
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 static int set_capacity(zpq_ctx *c, const DModel &layout, bool chain, bool lanes)
@@ -1276,7 +1288,8 @@ extern "C" int zpq_blockset_capacity_ex(zpq_ctx *c, const zpq_model *m, uint64_t
     static thread_local DModel layout;
     uint32_t sp = 0;
     const bool chain = set_layout(c, m, max_member_bytes, &layout, &sp);
-    // (ZPQ_SET_PIPE changes nothing here: any round of such a set may fall back to the chain encoder)
+    // (ZPQ_SET_PIPE changes nothing here: any round of such a set may fall back to the chain encoder; nor does ZPQ_SET_WAVES:
+    // workgroups of the wave kernels do not wait for one another either, memory alone bounds the set)
     const int rf = zpq_blockset_resolve_flags(m, flags);
     return set_capacity(c, layout, chain, rf > 0 && ((uint32_t)rf & ZPQ_SET_LANES) != 0);
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
@@ -1474,9 +1487,19 @@ static int set_segments(zpq_blockset *s, int decode, int n, const int32_t *membe
             c->last_name = name;
         } else {
             // the round in one launch of k_rows / k_lanes<..., KEEP>: any number of members, no workgroup waits for another
+            // ZPQ_SET_WAVES: this call runs on k_wset / k_wsetd unless ZPQ_ENC_GPIPE=0 / ZPQ_DEC_GPIPE=0 says otherwise right now;
+            // the slot format is one, so calls on a set may alternate.  No floor on k.
+            const char *ev = getenv(decode ? "ZPQ_DEC_GPIPE" : "ZPQ_ENC_GPIPE");
+            const bool waves = (s->flags & ZPQ_SET_WAVES) != 0 && !(ev && atoi(ev) == 0);
             HIPCK(hipEventRecord(c->ev0, st));
-            if ((rc = zpq_launch_lanes_keep(&B, &s->layout, decode, st)) != ZPQ_OK) return rc;
-            c->last_name = zpq_lanes_kernel_name(&s->layout, decode);
+            if (waves) {
+                const char *name = nullptr;
+                if ((rc = zpq_launch_wset(&B, &s->layout, decode, st, &name)) != ZPQ_OK) return rc;
+                c->last_name = name;
+            } else {
+                if ((rc = zpq_launch_lanes_keep(&B, &s->layout, decode, st)) != ZPQ_OK) return rc;
+                c->last_name = zpq_lanes_kernel_name(&s->layout, decode);
+            }
         }
         HIPCK(hipGetLastError());
         HIPCK(hipEventRecord(c->ev1, st));

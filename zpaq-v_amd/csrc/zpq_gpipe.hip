@@ -24,6 +24,8 @@
 // that sets the pace is the MIX over seven inputs; FETCH_SIZE + WRITE_SIZE = 2.15 + 1.60 TB per launch = 31 + 23 random
 // 64-byte lines per input byte (profiles/r03_gpipe_*.txt): the model's tables do not fit any cache at this residency, and
 // the kernel runs at ~41 G random lines/s.
+//
+// Block sets (ZPQ_SET_WAVES): k_wset<BATCH> / k_wsetd below are the state hand-over (KEEP) forms of k_gpipe / k_gdec.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -119,7 +121,9 @@ struct P8 {
 // One component wave.  The per-bit code is the reference's predict() + update() for this component's type, restated on
 // the block's tables in HBM (predictor.v:536-824; the CPU oracle's pred_predict / pred_update are the same text).
 // VM: the context of a byte comes from the ring the interpreter wave fills (k_vpipe), not from the hash chain in registers.
-template <int TYPE, bool BATCH, bool VM = false>
+// KEEP (block sets, k_wset): the lane's block goes on from what the last segment's launch left in its slot and hands its
+// state to the next one; see k_wset below.
+template <int TYPE, bool BATCH, bool VM = false, bool KEEP = false>
 __device__ __forceinline__ void comp_stage(const Stage &S)
 {
     const DBatch &B = *S.B;
@@ -178,6 +182,19 @@ __device__ __forceinline__ void comp_stage(const Stage &S)
     const bool batched = BATCH && TYPE != ZT_CONST && TYPE != ZT_AVG && !((TYPE == ZT_ICM || TYPE == ZT_ISSE) && ht_len < 8192u);
     u32 w_cur = 0;
     if (ci == 0 && S.active && S.nin) w_cur = *reinterpret_cast<const u32 *>(src_addr(0) & ~(uintptr_t)3);
+    if constexpr (KEEP) {
+        // What outlives a segment in the reference and lives in this wave's registers (zpq_lanes.hip, KEEP): the hash chain's
+        // previous byte -- every wave walks the chain and reads it, wave 0 writes it back -- and MATCH's scalars.  hctx starts
+        // from 0 (Predictor.reset: h[i] = 0); the byte MATCH builds is written whole at the byte's end, so ht[limit] needs no
+        // re-reading here.  Loaded before the wave's first barrier, stored behind its last.
+        if (S.active) {
+            prev = reinterpret_cast<const DVmRegs *>(S.slot + M.regs_off)->pad_[0];
+            if (TYPE == ZT_MATCH) {
+                const DCompScal &g = reinterpret_cast<const DCompScal *>(S.slot + M.scal_off)[ci];
+                ma = g.a; mb = g.b; mc = g.c; mlimit = g.limit; mcxt = g.cxt;
+            }
+        }
+    }
 
     for (u32 it = 0; it < S.iters; it++) {
         const u32 bi = it - (u32)ci;
@@ -625,6 +642,20 @@ __device__ __forceinline__ void comp_stage(const Stage &S)
 #endif
         lds_barrier();
     }
+    if constexpr (KEEP) {
+        // A lane works only while bi < ITS total, so the registers stand at its own segment's end however long the workgroup's
+        // longest member keeps the loop going.  Nothing else is buffered: a batched stage stores every entry it trained inside
+        // the byte that trained it (a bit-history row at each nibble's end, MIX / MIX2 / SSE / CM entries bit by bit).
+        // p[] (DCompScal::pad_[0]) is not written: every input of a model these kernels take is an earlier component, which
+        // has predicted this bit before its consumer reads it, so the p[] the lane kernels carry across segments is dead here.
+        if (S.active) {
+            if (ci == 0) reinterpret_cast<DVmRegs *>(S.slot + M.regs_off)->pad_[0] = prev;
+            if (TYPE == ZT_MATCH) {
+                DCompScal &g = reinterpret_cast<DCompScal *>(S.slot + M.scal_off)[ci];
+                g.a = ma; g.b = mb; g.c = mc; g.limit = mlimit; g.cxt = mcxt;
+            }
+        }
+    }
 }
 
 // the coder wave (encoder.v:48-139): byte it - n, predictions from the last component's ring; returns the bytes written
@@ -783,6 +814,71 @@ __global__ void __launch_bounds__(1024) k_gpipe(const DBatch B, const GCfg cfg)
     }
 }
 
+// Block sets (ZPQ_SET_WAVES): one segment of B.nblocks members of a set per launch, the state handed on through the member's
+// slot in the format k_rows / k_lanes<..., KEEP> keep (zpq_lanes.hip), so that the next call on a member may run on either
+// family.  Lane l of workgroup w codes entry i = 64 w + l of the call on slot B.slot_map[i]; lanes beyond B.nblocks read no
+// map entry, touch no slot and code nothing.  No rounds, no Predictor.init: k_set_init initialised the set once.  The byte
+// loops are comp_stage<..., KEEP = true> and coder_stage as they stand (a segment is a whole arithmetic-coded stream).
+template <bool BATCH>
+__global__ void __launch_bounds__(1024) k_wset(const DBatch B, const GCfg cfg)
+{
+    extern __shared__ __align__(16) u8 lds[];
+    const DModel &M = *B.model;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    {
+        u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
+        for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
+        u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
+        for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
+        for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
+        u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
+        for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
+        int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
+        for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
+    }
+    u32 *const misc = reinterpret_cast<u32 *>(lds + L_LINK + (size_t)cfg.ring * BPW * 16);
+    if (tid == 0) *misc = 0u;
+    __syncthreads();
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = cfg.n;
+    const int blk = blockIdx.x * BPW + lane;
+    const bool active = blk < B.nblocks;
+    const int slot_ix = active ? B.slot_map[blk] : 0;
+
+    Stage S;
+    S.B = &B; S.M = &M; S.lds = lds; S.ci = wave; S.lane = lane; S.n = n; S.cfg = &cfg; S.active = active;
+    S.slot = B.slots + (u64)slot_ix * M.slot_bytes;              // (an inactive lane never dereferences it)
+    S.src = active ? B.in + B.in_off[blk] : B.in;
+    S.nin = active ? (u32)(B.in_off[blk + 1] - B.in_off[blk]) : 0u;
+    S.dst = active ? B.out + B.out_off[blk] : B.out;
+    S.cap = active ? (u32)(B.out_off[blk + 1] - B.out_off[blk]) : 0u;
+    S.total = active ? S.nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u) : 0u;
+    if (wave == 0) atomicMax(misc, S.total);
+    __syncthreads();
+    S.iters = *misc + (u32)n;
+    S.hashes = cfg.hashes;
+    S.busy = 0;
+    if (wave < n) {
+        switch (M.comp[wave].type) {                             // uniform per wave
+        case ZT_CONST: comp_stage<ZT_CONST, BATCH, false, true>(S); break;
+        case ZT_CM: comp_stage<ZT_CM, BATCH, false, true>(S); break;
+        case ZT_ICM: comp_stage<ZT_ICM, BATCH, false, true>(S); break;
+        case ZT_MATCH: comp_stage<ZT_MATCH, BATCH, false, true>(S); break;
+        case ZT_AVG: comp_stage<ZT_AVG, BATCH, false, true>(S); break;
+        case ZT_MIX2: comp_stage<ZT_MIX2, BATCH, false, true>(S); break;
+        case ZT_MIX: comp_stage<ZT_MIX, BATCH, false, true>(S); break;
+        case ZT_ISSE: comp_stage<ZT_ISSE, BATCH, false, true>(S); break;
+        default: comp_stage<ZT_SSE, BATCH, false, true>(S); break;
+        }
+    } else {
+        const u32 opos = coder_stage(S);
+        if (active) {
+            B.out_len[blk] = opos;
+            B.status[blk] = opos > S.cap ? ZPQ_E_OVERFLOW : ZPQ_OK;
+        }
+    }
+}
+
 
 // ================================================================================================================
 // The DECODER of the same models: wave i = component i of the workgroup's 64 blocks (lane = block), the last wave = the
@@ -823,7 +919,8 @@ struct DStage {
 };
 
 // VM: the context of a byte is read from LDS (k_vdec), not computed by the hash chain in registers.
-template <int TYPE, bool VM = false>
+// KEEP (block sets, k_wsetd): as in comp_stage.
+template <int TYPE, bool VM = false, bool KEEP = false>
 __device__ __forceinline__ void comp_dec(const DStage &S)
 {
     const DModel &M = *S.M;
@@ -892,6 +989,15 @@ __device__ __forceinline__ void comp_dec(const DStage &S)
     u32 nrow = 0;
     (void)ra; (void)rb; (void)sok0; (void)sok1; (void)nrow_ok; (void)nrow;
     (void)spec; (void)sa0; (void)sb0; (void)tr_a; (void)tr0; (void)tr1; (void)yprev; (void)trw;
+    if constexpr (KEEP) {                                        // (see comp_stage; before the wave's first barrier)
+        if (S.active) {
+            prev = reinterpret_cast<const DVmRegs *>(S.slot + M.regs_off)->pad_[0];
+            if (TYPE == ZT_MATCH) {
+                const DCompScal &g = reinterpret_cast<const DCompScal *>(S.slot + M.scal_off)[ci];
+                ma = g.a; mb = g.b; mc = g.c; mlimit = g.limit;
+            }
+        }
+    }
 
     for (;;) {
         lds_barrier();                                           // the decoder wave has looked at the EOF flag
@@ -1166,7 +1272,21 @@ __device__ __forceinline__ void comp_dec(const DStage &S)
             u32 a = byte;
             for (u32 k = 0; k < hash_steps; k++) a = (a + prev + 512u) * 773u;
             hctx = hash_steps ? a : 0u;
-            prev = byte;
+            if (!KEEP || alive) prev = byte;                     // (a lane whose block has ended sees bits of 0 while its neighbours go on)
+        }
+    }
+    if constexpr (KEEP) {
+        // A lane's registers stop at the byte boundary where its block met the EOF flag (or overflowed: that member has failed),
+        // whatever the rest of the workgroup went on to decode.  Nothing is buffered beyond them: every trained entry was stored
+        // by the bit that trained it (tr_* and the SSE rows in LDS are copies of what the tables hold), a bit-history row at its
+        // nibble's end, and a segment ends on a byte boundary.  MATCH's bit position (DCompScal::cxt) is 0 there and in the slot.
+        // p[] is dead for these models (comp_stage).
+        if (S.active) {
+            if (ci == 0) reinterpret_cast<DVmRegs *>(S.slot + M.regs_off)->pad_[0] = prev;
+            if (TYPE == ZT_MATCH) {
+                DCompScal &g = reinterpret_cast<DCompScal *>(S.slot + M.scal_off)[ci];
+                g.a = ma; g.b = mb; g.c = mc; g.limit = mlimit; g.cxt = 0;
+            }
         }
     }
 }
@@ -1332,6 +1452,52 @@ __global__ void __launch_bounds__(1024) k_gdec(const DBatch B, const GCfg cfg)
 #endif
         __syncthreads();
     }
+}
+
+// Block sets (ZPQ_SET_WAVES), decoding: as k_wset.  64 lanes per workgroup (ZPQ_GDEC_BPW is not read).
+__global__ void __launch_bounds__(1024) k_wsetd(const DBatch B, const GCfg cfg)
+{
+    extern __shared__ __align__(16) u8 lds[];
+    const DModel &M = *B.model;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    {
+        u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
+        for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
+        u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
+        for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
+        for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
+        u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
+        for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
+        int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
+        for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
+    }
+    __syncthreads();
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = cfg.n;
+    const int blk = blockIdx.x * BPW + lane;
+    const bool active = blk < B.nblocks;
+    const int slot_ix = active ? B.slot_map[blk] : 0;
+    DStage S;
+    S.B = &B; S.M = &M; S.lds = lds; S.cfg = &cfg; S.ci = wave; S.lane = lane; S.n = n; S.active = active; S.blk = blk;
+    S.slot = B.slots + (u64)slot_ix * M.slot_bytes;              // (an inactive lane never dereferences it)
+    S.src = active ? B.in + B.in_off[blk] : B.in;
+    S.nin = active ? (u32)(B.in_off[blk + 1] - B.in_off[blk]) : 0u;
+    S.dst = active ? B.out + B.out_off[blk] : B.out;
+    S.cap = active ? (u32)(B.out_off[blk + 1] - B.out_off[blk]) : 0u;
+    S.prof[0] = S.prof[1] = S.prof[2] = S.prof[3] = 0;
+    if (wave < n) {
+        switch (M.comp[wave].type) {                             // uniform per wave
+        case ZT_CONST: comp_dec<ZT_CONST, false, true>(S); break;
+        case ZT_CM: comp_dec<ZT_CM, false, true>(S); break;
+        case ZT_ICM: comp_dec<ZT_ICM, false, true>(S); break;
+        case ZT_MATCH: comp_dec<ZT_MATCH, false, true>(S); break;
+        case ZT_AVG: comp_dec<ZT_AVG, false, true>(S); break;
+        case ZT_MIX2: comp_dec<ZT_MIX2, false, true>(S); break;
+        case ZT_MIX: comp_dec<ZT_MIX, false, true>(S); break;
+        case ZT_ISSE: comp_dec<ZT_ISSE, false, true>(S); break;
+        default: comp_dec<ZT_SSE, false, true>(S); break;
+        }
+    } else coder_dec(S);
 }
 
 
@@ -1680,14 +1846,20 @@ static void vpipe_offsets(zpqg::VCfg *V, size_t lds_total, int ctx_words, int hd
     V->ctx_off = V->stat_off - ctx_words * 4;
 }
 
+// The envelope of k_gpipe / k_wset from the model's shape alone (no environment variable enters it)
+extern "C" int zpq_gpipe_shape_applies(const DModel *M)
+{
+    zpqg::GCfg cfg;
+    size_t lds = 0;
+    return gpipe_cfg(M, &cfg, &lds) ? 1 : 0;
+}
+
 // ZPQ_ENC_GPIPE=0 keeps general models on zpq_lanes.hip (tests compare the two)
 extern "C" int zpq_gpipe_applies(const DModel *M)
 {
     const char *ev = getenv("ZPQ_ENC_GPIPE");
     if (ev && atoi(ev) == 0) return 0;
-    zpqg::GCfg cfg;
-    size_t lds = 0;
-    return gpipe_cfg(M, &cfg, &lds) ? 1 : 0;
+    return zpq_gpipe_shape_applies(M);
 }
 
 // Workgroups of `threads` threads and `lds` bytes that one CU keeps resident: what the runtime says for the compiled kernel
@@ -1731,14 +1903,20 @@ extern "C" int zpq_launch_gpipe(const DBatch *B, const DModel *hostM, int nslots
     return ZPQ_OK;
 }
 
-// ---- the decoder (k_gdec).  ZPQ_DEC_GPIPE=0 keeps general models' decoding on zpq_lanes.hip.
+// ---- the decoder (k_gdec).  Its envelope (and k_wsetd's) from the model's shape alone:
+extern "C" int zpq_gdec_shape_applies(const DModel *M)
+{
+    zpqg::GCfg cfg;
+    size_t lds = 0, dlds = 0;
+    return gpipe_cfg(M, &cfg, &lds, &dlds) && dlds <= 160 * 1024 ? 1 : 0;
+}
+
+// ZPQ_DEC_GPIPE=0 keeps general models' decoding on zpq_lanes.hip.
 extern "C" int zpq_gdec_applies(const DModel *M)
 {
     const char *ev = getenv("ZPQ_DEC_GPIPE");
     if (ev && atoi(ev) == 0) return 0;
-    zpqg::GCfg cfg;
-    size_t lds = 0, dlds = 0;
-    return gpipe_cfg(M, &cfg, &lds, &dlds) && dlds <= 160 * 1024 ? 1 : 0;
+    return zpq_gdec_shape_applies(M);
 }
 
 static int gdec_wgs_per_cu(const zpqg::GCfg &cfg, size_t dlds)
@@ -1772,6 +1950,36 @@ extern "C" int zpq_launch_gdec(const DBatch *B, const DModel *hostM, int nslots,
     const int nwg = (nslots + bpw - 1) / bpw;
     (void)hipFuncSetAttribute((const void *)zpqg::k_gdec, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipLaunchKernelGGL(zpqg::k_gdec, dim3(nwg), dim3(64 * (cfg.n + 1)), dlds, stream, *B, cfg);
+    return ZPQ_OK;
+}
+
+// ---- block sets on the wave kernels (ZPQ_SET_WAVES): one segment of B->nblocks members in one launch of k_wset / k_wsetd,
+// entry i on slot B->slot_map[i].  The caller has checked the envelope (zpq_blockset_waves_applies) and this call's
+// ZPQ_ENC_GPIPE / ZPQ_DEC_GPIPE; ZPQ_GPIPE_BATCH=0 selects the bit-serial encoder stages as for k_gpipe; the decoder always
+// runs 64 lanes per workgroup (ZPQ_GDEC_BPW is not read: a wave costs the same whatever its lanes in use, zpq_launch_gdec).
+extern "C" int zpq_launch_wset(const DBatch *B, const DModel *hostM, int decode, hipStream_t stream, const char **name)
+{
+    zpqg::GCfg cfg;
+    size_t lds = 0, dlds = 0;
+    if (!gpipe_cfg(hostM, &cfg, &lds, &dlds) || dlds > 160 * 1024) return ZPQ_E_INTERNAL;
+    if (B->nblocks < 1 || B->nslots != B->nblocks || !B->slot_map) return ZPQ_E_INTERNAL;   // (no identity map: the slots are the set's)
+    cfg.bpw = zpqg::BPW;
+    const dim3 g((B->nblocks + zpqg::BPW - 1) / zpqg::BPW), t(64 * (cfg.n + 1));
+    if (decode) {
+        (void)hipFuncSetAttribute((const void *)zpqg::k_wsetd, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipLaunchKernelGGL(zpqg::k_wsetd, g, t, dlds, stream, *B, cfg);
+        *name = "k_wsetd<decode>";
+        return ZPQ_OK;
+    }
+    const char *ev = getenv("ZPQ_GPIPE_BATCH");
+    if (ev && atoi(ev) == 0) {
+        (void)hipFuncSetAttribute((const void *)zpqg::k_wset<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipLaunchKernelGGL(zpqg::k_wset<false>, g, t, lds, stream, *B, cfg);
+    } else {
+        (void)hipFuncSetAttribute((const void *)zpqg::k_wset<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipLaunchKernelGGL(zpqg::k_wset<true>, g, t, lds, stream, *B, cfg);
+    }
+    *name = "k_wset<encode>";
     return ZPQ_OK;
 }
 
