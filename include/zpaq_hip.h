@@ -265,7 +265,12 @@ int zpq_block_decode_segment(zpq_block *, const uint8_t *in, size_t n, uint32_t 
  *                         any order (NULL = 0 .. n-1); the other arguments as for zpq_encode_blocks / zpq_decode_blocks,
  *                         entry i belonging to member[i].  Host pointers, synchronous on the ctx stream.
  * A member whose segment ends with a status other than ZPQ_OK (ZPQ_E_OVERFLOW, ZPQ_E_TOOBIG, ZPQ_E_VMSTEPS) has FAILED:
- * later calls report that status for it without coding, the other members are untouched.  ZPQ_FLAG_NOEOF: ZPQ_E_ARG.
+ * later calls report that status for it without coding (out_len, consumed and final_code 0, first_byte 0xFFFFFFFF), the other
+ * members are untouched.  ZPQ_FLAG_NOEOF: ZPQ_E_ARG.
+ * The rest of a slab: a call in which every listed member is live copies the whole of out[out_off[0] .. out_off[n]) back, as
+ * the batch calls do for pageable buffers -- the bytes of a slab from min(out_len[i], cap) on are unspecified, nothing at or
+ * past out_off[n] is written.  A call in which a listed member has failed before copies only the stored bytes of each live
+ * member, min(out_len[i], cap) of them: every other byte of `out`, the failed members' slabs included, stays as it was.
  * Lifetime as for zpq_block: the ctx orphans its sets (calls then return ZPQ_E_CLOSED), a set keeps its model alive.
  *
  * Models no chain kernel takes are coded by the lane-0 kernel, ONE LAUNCH PER MEMBER.  zpq_blockset_create_ex /

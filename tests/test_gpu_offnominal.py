@@ -60,6 +60,22 @@ def raw_encode(zpq, ctx, model, blocks, caps, flags):
     return out, out_off, out_len, status
 
 
+def raw_set_decode(zpq, bs, streams, caps, flags, members=None):
+    """zpq_blockset_decode_segments on set `bs` with a slab size per member (the binding takes one per call), the output
+    sentinel-filled with a pad behind the last slab.  Returns what raw_decode returns."""
+    n = len(streams)
+    src, in_off, out_off = _source(streams), _offsets([len(s) for s in streams]), _offsets(caps)
+    out = np.full(int(out_off[-1]) + PAD, SENTINEL, dtype=np.uint8)
+    u32 = [np.zeros(n, dtype=np.uint32) for _ in range(4)]
+    status = np.full(n, -99, dtype=np.int32)
+    mem = None if members is None else np.asarray(members, dtype=np.int32)
+    rc = zpq.lib().zpq_blockset_decode_segments(bs.h, n, None if mem is None else mem.ctypes.data, src.ctypes.data,
+                                                in_off.ctypes.data, flags, out.ctypes.data, out_off.ctypes.data, u32[0].ctypes.data,
+                                                u32[1].ctypes.data, u32[2].ctypes.data, u32[3].ctypes.data, status.ctypes.data)
+    assert rc == 0, "library call failed: %d" % rc
+    return (out, out_off) + tuple(u32) + (status,)
+
+
 def dev_call(zpq, ctx, model, decode, streams, caps, flags):
     """The device-pointer form on an output tensor filled with the sentinel, a pad of it behind the last slab."""
     import torch
@@ -377,7 +393,6 @@ def test_blockset_follows_damaged_segments_per_member(zpq, gpu_ctx, monkeypatch)
     model = zpq.Model(header=hdr)
     bs = zpq.BlockSet(gpu_ctx, model, nm, max_member_bytes=8192)
     oracles = [O.Codec(hdr) for _ in range(nm)]
-    L = zpq.lib()
     try:
         for seg in range(3):
             streams = [coded[m][seg] for m in range(nm)]
@@ -389,17 +404,10 @@ def test_blockset_follows_damaged_segments_per_member(zpq, gpu_ctx, monkeypatch)
                 assert want[7].status == -7 and want[3].status == 0 and want[3].out_len != len(data[3][1])
             if seg == 2:
                 want[7] = OC.Expected(-7, 0, b"", 0, 0, OC.NO_BYTE)         # failed: reported without coding
-            src, in_off, out_off = _source(streams), _offsets([len(s) for s in streams]), _offsets(caps)
-            out = np.full(int(out_off[-1]) + PAD, SENTINEL, dtype=np.uint8)
-            u32 = [np.zeros(nm, dtype=np.uint32) for _ in range(4)]
-            status = np.full(nm, -99, dtype=np.int32)
-            rc = L.zpq_blockset_decode_segments(bs.h, nm, None, src.ctypes.data, in_off.ctypes.data, zpq.FLAG_PP, out.ctypes.data,
-                                                out_off.ctypes.data, u32[0].ctypes.data, u32[1].ctypes.data, u32[2].ctypes.data,
-                                                u32[3].ctypes.data, status.ctypes.data)
-            assert rc == 0, "library call failed: %d" % rc
+            got = raw_set_decode(zpq, bs, streams, caps, zpq.FLAG_PP)
             assert gpu_ctx.last_kernel_name == "k_chain<decode>"
             batch = [OC.Case("segment", "member %d segment %d" % (m, seg), streams[m], len(data[m][seg])) for m in range(nm)]
-            check_decode("blockset segment %d" % seg, batch, caps, want, (out, out_off) + tuple(u32) + (status,))
+            check_decode("blockset segment %d" % seg, batch, caps, want, got)
             for m in range(nm):
                 if seg == 0 or m not in (3, 7):                              # (the undamaged ones are the data)
                     assert want[m].data == data[m][seg] and want[m].status == 0, (seg, m)
