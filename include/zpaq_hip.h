@@ -62,7 +62,9 @@ extern "C" {
                                  (host, _dev, _multi) honour it, and zpq_ctx_resident_capacity answers for the pair
                                  it selects.  zpq_block_* and zpq_blockset_* ignore both the flag and the variable: a
                                  block's first segment runs on the batch kernel it ran on before (k_rows for such a
-                                 model), later segments and block sets on k_generic.  The environment decides first:
+                                 model), later segments on k_generic; a block set runs on k_generic, or on k_rows /
+                                 k_lanes under ZPQ_SET_LANES.  The way onto these kernels' state hand-over forms for a
+                                 block set is the set's own flag, ZPQ_SET_VMWAVES (below).  The environment decides first:
                                  ZPQ_VM_PIPE=1 sets it for every call, ZPQ_VM_PIPE=0 clears it (a value that starts
                                  with neither digit decides nothing). */
 
@@ -312,15 +314,40 @@ int zpq_block_decode_segment(zpq_block *, const uint8_t *in, size_t n, uint32_t 
  *                         ("k_wset<encode>" / "k_wsetd<decode>").  The capacity stays that of ZPQ_SET_LANES: memory alone.
  *                         ZPQ_SET_WAVES=1 / =0 in the environment by the rule of ZPQ_SET_LANES, resolved on its own and then
  *                         combined: a process that wants it from the environment sets both variables.
+ *   ZPQ_SET_VMWAVES       the same request for a model whose HCOMP program is NOT the shipped hash chain: run the calls of the
+ *                         set on the state hand-over forms of k_vpipe / k_vdec (k_vset / k_vsetd: a wave per component, one
+ *                         for the coder and one that runs the ZPAQL interpreter, a lane per member).  Honoured where
+ *                         ZPQ_SET_LANES is in force for the set (flag or environment, and honoured) and
+ *                         zpq_blockset_vmwaves_applies(model): the lanes predicate, and the model is in the envelope of
+ *                         ZPQ_FLAG_VMPIPE -- not the hash chain, at most 14 components, every input an earlier component, a
+ *                         MIX of 1-8 inputs, both directions' LDS (rings, contexts, header) within 160 KiB; its shape alone,
+ *                         no environment variable and no batch size enter it.  Otherwise it decides nothing.  A honoured set
+ *                         reports ZPQ_SET_LANES | ZPQ_SET_VMWAVES (65).  No model can have both this and ZPQ_SET_WAVES (the
+ *                         HCOMP program decides): a caller who wants the wave kernels wherever they apply passes
+ *                         ZPQ_SET_LANES | ZPQ_SET_WAVES | ZPQ_SET_VMWAVES (81), which resolves to 17 or to 65.  Everything
+ *                         else is as for ZPQ_SET_WAVES: the choice per call (an encode call under ZPQ_ENC_GPIPE=0, a decode
+ *                         call under ZPQ_DEC_GPIPE=0 runs on k_rows / k_lanes, the slots hold one format), no floor on the
+ *                         number of members, ZPQ_GPIPE_BATCH=0, ZPQ_GDEC_BPW ignored, the same coded bytes, ZPQ_E_VMSTEPS
+ *                         ahead of ZPQ_E_OVERFLOW as in plain batches, the capacity of ZPQ_SET_LANES, and the names
+ *                         "k_vset<encode>" / "k_vsetd<decode>".  ZPQ_SET_VMWAVES=1 / =0 in the environment by the rule of
+ *                         ZPQ_SET_LANES, resolved on its own and then combined.
+ *                         Whether the request pays depends on the PROGRAM, not on the number of members (measured at 16, 512
+ *                         and 4096 members, 4 KiB segments, tools/set_vmwaves_bench.py): behind a program as light as the hash
+ *                         chain (C4b's components, `a=a` in front of it) a round takes 2.3-2.8x less kernel time to encode
+ *                         and 1.35-1.55x less to decode than on k_rows, from 16 members on; behind a program that loops
+ *                         1-16 times per byte (zpaql_programs "loop_count") it LOSES at every member count measured, 16
+ *                         included (encode 7-37 %, decode 16-51 % slower): one wave runs the 64 members' interpreters in
+ *                         lockstep, k_rows one interpreter per row of lanes.  Leave such sets on ZPQ_SET_LANES alone.
  *   zpq_blockset_flags    the ZPQ_SET_* in force for a set (0 for a request that decided nothing).  Like every call on a
  *                         set it must not race with zpq_blockset_destroy of the same handle.
- *   zpq_blockset_lanes_applies / _pipe_applies / _waves_applies / zpq_blockset_resolve_flags   host logic only, no device
+ *   zpq_blockset_lanes_applies / _pipe_applies / _waves_applies / _vmwaves_applies / zpq_blockset_resolve_flags   host logic only, no device
  *                         needed: would the request be honoured for this model (its shape alone, neither a batch size nor
  *                         the environment); the flags a set created with `flags` would get (environment applied).
  */
 #define ZPQ_SET_LANES 1u
 #define ZPQ_SET_PIPE 4u
 #define ZPQ_SET_WAVES 16u
+#define ZPQ_SET_VMWAVES 64u
 typedef struct zpq_blockset zpq_blockset;
 int zpq_blockset_create(zpq_ctx *, const zpq_model *, int nmembers, uint64_t max_member_bytes, zpq_blockset **out);
 int zpq_blockset_create_ex(zpq_ctx *, const zpq_model *, int nmembers, uint64_t max_member_bytes, uint32_t flags, zpq_blockset **out);
@@ -331,6 +358,7 @@ unsigned zpq_blockset_flags(const zpq_blockset *);
 int zpq_blockset_lanes_applies(const zpq_model *);
 int zpq_blockset_pipe_applies(const zpq_model *);
 int zpq_blockset_waves_applies(const zpq_model *);
+int zpq_blockset_vmwaves_applies(const zpq_model *);
 int zpq_blockset_resolve_flags(const zpq_model *, uint32_t flags);
 int zpq_blockset_encode_segments(zpq_blockset *, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
                                  uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status);

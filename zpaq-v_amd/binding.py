@@ -19,6 +19,7 @@ FLAG_VMPIPE = 16
 SET_LANES = 1                                # zpq_blockset_create_ex / zpq_blockset_capacity_ex
 SET_PIPE = 4
 SET_WAVES = 16
+SET_VMWAVES = 64
 _LIB = None
 # Handle lifetime on the Python side (the C side tolerates any destroy order as well, include/zpaq_hip.h): every live
 # Context, Block and PinnedArray is tracked; Context.close() closes its blocks first; at interpreter exit everything
@@ -128,6 +129,7 @@ def lib():
     L.zpq_blockset_lanes_applies.argtypes = [vp]
     L.zpq_blockset_pipe_applies.argtypes = [vp]
     L.zpq_blockset_waves_applies.argtypes = [vp]
+    L.zpq_blockset_vmwaves_applies.argtypes = [vp]
     L.zpq_blockset_resolve_flags.argtypes = [vp, u32]
     L.zpq_blockset_encode_segments.argtypes = [vp, i32, vp, vp, vp, u32, vp, vp, vp, vp]
     L.zpq_blockset_decode_segments.argtypes = [vp, i32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
@@ -303,10 +305,10 @@ class Context:
             raise ZpqError(n, "zpq_ctx_resident_capacity")
         return n
 
-    def blockset_capacity(self, model, max_member_bytes=0, lanes=False, pipe=False, waves=False):
-        """Members one BlockSet of `model` may hold on this GPU (zpq_blockset_capacity_ex; lanes / pipe / waves: with
-        SET_LANES / SET_PIPE / SET_LANES | SET_WAVES requested)."""
-        n = lib().zpq_blockset_capacity_ex(self.h, model.h, max_member_bytes, _set_flags(lanes, pipe, waves))
+    def blockset_capacity(self, model, max_member_bytes=0, lanes=False, pipe=False, waves=False, vmwaves=False):
+        """Members one BlockSet of `model` may hold on this GPU (zpq_blockset_capacity_ex; lanes / pipe / waves / vmwaves: with
+        SET_LANES / SET_PIPE / SET_LANES | SET_WAVES / SET_LANES | SET_VMWAVES requested)."""
+        n = lib().zpq_blockset_capacity_ex(self.h, model.h, max_member_bytes, _set_flags(lanes, pipe, waves, vmwaves))
         if n < 0:
             raise ZpqError(n, "zpq_blockset_capacity")
         return n
@@ -424,8 +426,9 @@ class Block:
         return out.raw[:olen.value], cons.value, code.value, first.value
 
 
-def _set_flags(lanes, pipe, waves):
-    return (SET_LANES if lanes or waves else 0) | (SET_PIPE if pipe else 0) | (SET_WAVES if waves else 0)
+def _set_flags(lanes, pipe, waves, vmwaves=False):
+    return ((SET_LANES if lanes or waves or vmwaves else 0) | (SET_PIPE if pipe else 0) | (SET_WAVES if waves else 0)
+            | (SET_VMWAVES if vmwaves else 0))
 
 
 class BlockSet:
@@ -436,17 +439,20 @@ class BlockSet:
     read-only `lanes` tells whether the library honoured it.  pipe=True requests the wave-pipelined encoder for a chain
     model (ZPQ_SET_PIPE: encode calls with at least 12 live members; same coded bytes); read-only `pipe` likewise.
     waves=True requests, with lanes, the wave-per-component kernels (ZPQ_SET_LANES | ZPQ_SET_WAVES: k_wset / k_wsetd for a
-    model both take; same coded bytes); read-only `waves` likewise."""
+    model both take; same coded bytes); read-only `waves` likewise.  vmwaves=True requests, with lanes, the same for a
+    model whose HCOMP program is not the shipped hash chain (ZPQ_SET_LANES | ZPQ_SET_VMWAVES: k_vset / k_vsetd, with a wave
+    that runs the ZPAQL interpreter; same coded bytes); read-only `vmwaves` likewise.  No model gets both."""
 
-    def __init__(self, ctx, model, nmembers, max_member_bytes=0, lanes=False, pipe=False, waves=False):
+    def __init__(self, ctx, model, nmembers, max_member_bytes=0, lanes=False, pipe=False, waves=False, vmwaves=False):
         self.ctx, self.model, self.nmembers = ctx, model, nmembers
         self.h = C.c_void_p()
         _ck(lib().zpq_blockset_create_ex(ctx.h, model.h, nmembers, max_member_bytes,
-                                         _set_flags(lanes, pipe, waves), C.byref(self.h)),
+                                         _set_flags(lanes, pipe, waves, vmwaves), C.byref(self.h)),
             "zpq_blockset_create")
         self._lanes = bool(lib().zpq_blockset_flags(self.h) & SET_LANES)
         self._pipe = bool(lib().zpq_blockset_flags(self.h) & SET_PIPE)
         self._waves = bool(lib().zpq_blockset_flags(self.h) & SET_WAVES)
+        self._vmwaves = bool(lib().zpq_blockset_flags(self.h) & SET_VMWAVES)
         ctx._children.add(self)
 
     @property
@@ -460,6 +466,10 @@ class BlockSet:
     @property
     def waves(self):
         return self._waves
+
+    @property
+    def vmwaves(self):
+        return self._vmwaves
 
     def close(self):
         if getattr(self, "h", None) and _LIB is not None:

@@ -33,10 +33,11 @@ extern "C" void zpq_launch_generic(const DBatch *B, const DModel *hostM, int dec
 extern "C" int zpq_generic_blocks_per_cu(const DModel *M);
 extern "C" int zpq_lanes_supported(const DModel *M);
 extern "C" int zpq_pipe_shape_applies(const DModel *M);   // zpq_pipe.hip: the chain is one of the shapes k_pipe codes
-#define ZPQ_SET_ALL (ZPQ_SET_LANES | ZPQ_SET_PIPE | ZPQ_SET_WAVES)
+#define ZPQ_SET_ALL (ZPQ_SET_LANES | ZPQ_SET_PIPE | ZPQ_SET_WAVES | ZPQ_SET_VMWAVES)
 extern "C" int zpq_launch_lanes_set_init(const DModel *d_model, const uint32_t *d_img, uint8_t *slots, int nmembers, hipStream_t stream);
 extern "C" int zpq_launch_lanes_keep(const DBatch *B, const DModel *hostM, int decode, hipStream_t stream);
 extern "C" int zpq_launch_wset(const DBatch *B, const DModel *hostM, int decode, hipStream_t stream, const char **name);   // ZPQ_SET_WAVES: k_wset / k_wsetd
+extern "C" int zpq_launch_vset(const DBatch *B, const DModel *hostM, int decode, hipStream_t stream, const char **name);   // ZPQ_SET_VMWAVES: k_vset / k_vsetd
 extern "C" int zpq_gpipe_shape_applies(const DModel *M);        // the envelopes of the wave kernels from the model's shape alone
 extern "C" int zpq_gdec_shape_applies(const DModel *M);
 extern "C" int zpq_lanes_blocks_per_cu(const DModel *M);
@@ -205,7 +206,8 @@ struct zpq_block {
 // lives in the set's own slots, in the layout chosen when the set is made: chain models on k_chain<..., KEEP> (dense tables
 // or the line store, sized by max_member_bytes), every other model on k_generic with ZB_KEEP_STATE, a launch per member --
 // or, on request (ZPQ_SET_LANES) and with at most 64 components, on the KEEP forms of k_rows / k_lanes, a launch per round;
-// with ZPQ_SET_WAVES on top, and a model both wave-per-component kernels take, on k_wset / k_wsetd (zpq_gpipe.hip), call by call.
+// with ZPQ_SET_WAVES on top, and a model both wave-per-component kernels take, on k_wset / k_wsetd (zpq_gpipe.hip), call by call;
+// with ZPQ_SET_VMWAVES on top, and a model the interpreter-wave pair takes, on k_vset / k_vsetd, call by call.
 struct zpq_blockset {
     zpq_ctx *ctx = nullptr;        // nullptr once the ctx has been destroyed (orphaned set)
     const zpq_model *model = nullptr;   // the set holds a reference
@@ -1252,6 +1254,14 @@ extern "C" int zpq_blockset_waves_applies(const zpq_model *m) try
 {
     return zpq_blockset_lanes_applies(m) && zpq_gpipe_shape_applies(&m->d) && zpq_gdec_shape_applies(&m->d) ? 1 : 0;
 } ZPQ_CATCH(return 0)
+// ZPQ_SET_VMWAVES, the same request for the models whose HCOMP program is not the shipped hash chain: honoured where
+// ZPQ_SET_LANES is in force and k_vpipe / k_vdec take the model (vpipe_cfg: the shape alone, one envelope for both directions).
+// ZPQ_SET_VMWAVES=1 / =0 in the environment by the same rule.  No model can have both this and ZPQ_SET_WAVES: the hash chain
+// decides between them.
+extern "C" int zpq_blockset_vmwaves_applies(const zpq_model *m) try
+{
+    return zpq_blockset_lanes_applies(m) && zpq_vpipe_applies(&m->d) ? 1 : 0;
+} ZPQ_CATCH(return 0)
 static bool set_request(const char *var, uint32_t flags, uint32_t bit)
 {
     const char *ev = getenv(var);
@@ -1264,7 +1274,8 @@ extern "C" int zpq_blockset_resolve_flags(const zpq_model *m, uint32_t flags) tr
     const bool lanes = set_request("ZPQ_SET_LANES", flags, ZPQ_SET_LANES) && zpq_blockset_lanes_applies(m);
     const bool pipe = set_request("ZPQ_SET_PIPE", flags, ZPQ_SET_PIPE) && zpq_blockset_pipe_applies(m);
     const bool waves = lanes && set_request("ZPQ_SET_WAVES", flags, ZPQ_SET_WAVES) && zpq_blockset_waves_applies(m);
-    return (int)((lanes ? ZPQ_SET_LANES : 0u) | (pipe ? ZPQ_SET_PIPE : 0u) | (waves ? ZPQ_SET_WAVES : 0u));
+    const bool vmwaves = lanes && set_request("ZPQ_SET_VMWAVES", flags, ZPQ_SET_VMWAVES) && zpq_blockset_vmwaves_applies(m);
+    return (int)((lanes ? ZPQ_SET_LANES : 0u) | (pipe ? ZPQ_SET_PIPE : 0u) | (waves ? ZPQ_SET_WAVES : 0u) | (vmwaves ? ZPQ_SET_VMWAVES : 0u));
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 static int set_capacity(zpq_ctx *c, const DModel &layout, bool chain, bool lanes)
@@ -1288,7 +1299,7 @@ extern "C" int zpq_blockset_capacity_ex(zpq_ctx *c, const zpq_model *m, uint64_t
     static thread_local DModel layout;
     uint32_t sp = 0;
     const bool chain = set_layout(c, m, max_member_bytes, &layout, &sp);
-    // (ZPQ_SET_PIPE changes nothing here: any round of such a set may fall back to the chain encoder; nor does ZPQ_SET_WAVES:
+    // (ZPQ_SET_PIPE changes nothing here: any round of such a set may fall back to the chain encoder; nor do ZPQ_SET_WAVES / _VMWAVES:
     // workgroups of the wave kernels do not wait for one another either, memory alone bounds the set)
     const int rf = zpq_blockset_resolve_flags(m, flags);
     return set_capacity(c, layout, chain, rf > 0 && ((uint32_t)rf & ZPQ_SET_LANES) != 0);
@@ -1488,13 +1499,14 @@ static int set_segments(zpq_blockset *s, int decode, int n, const int32_t *membe
         } else {
             // the round in one launch of k_rows / k_lanes<..., KEEP>: any number of members, no workgroup waits for another
             // ZPQ_SET_WAVES: this call runs on k_wset / k_wsetd unless ZPQ_ENC_GPIPE=0 / ZPQ_DEC_GPIPE=0 says otherwise right now;
-            // the slot format is one, so calls on a set may alternate.  No floor on k.
+            // the slot format is one, so calls on a set may alternate.  No floor on k.  ZPQ_SET_VMWAVES: the same with k_vset / k_vsetd.
             const char *ev = getenv(decode ? "ZPQ_DEC_GPIPE" : "ZPQ_ENC_GPIPE");
-            const bool waves = (s->flags & ZPQ_SET_WAVES) != 0 && !(ev && atoi(ev) == 0);
+            const bool on = !(ev && atoi(ev) == 0);
+            const bool waves = (s->flags & ZPQ_SET_WAVES) != 0 && on, vmwaves = (s->flags & ZPQ_SET_VMWAVES) != 0 && on;
             HIPCK(hipEventRecord(c->ev0, st));
-            if (waves) {
+            if (waves || vmwaves) {
                 const char *name = nullptr;
-                if ((rc = zpq_launch_wset(&B, &s->layout, decode, st, &name)) != ZPQ_OK) return rc;
+                if ((rc = (waves ? zpq_launch_wset : zpq_launch_vset)(&B, &s->layout, decode, st, &name)) != ZPQ_OK) return rc;
                 c->last_name = name;
             } else {
                 if ((rc = zpq_launch_lanes_keep(&B, &s->layout, decode, st)) != ZPQ_OK) return rc;

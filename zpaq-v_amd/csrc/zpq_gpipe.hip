@@ -25,7 +25,8 @@
 // 64-byte lines per input byte (profiles/r03_gpipe_*.txt): the model's tables do not fit any cache at this residency, and
 // the kernel runs at ~41 G random lines/s.
 //
-// Block sets (ZPQ_SET_WAVES): k_wset<BATCH> / k_wsetd below are the state hand-over (KEEP) forms of k_gpipe / k_gdec.
+// Block sets (ZPQ_SET_WAVES): k_wset<BATCH> / k_wsetd below are the state hand-over (KEEP) forms of k_gpipe / k_gdec;
+// (ZPQ_SET_VMWAVES): k_vset<BATCH> / k_vsetd those of k_vpipe / k_vdec.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -188,7 +189,7 @@ __device__ __forceinline__ void comp_stage(const Stage &S)
         // from 0 (Predictor.reset: h[i] = 0); the byte MATCH builds is written whole at the byte's end, so ht[limit] needs no
         // re-reading here.  Loaded before the wave's first barrier, stored behind its last.
         if (S.active) {
-            prev = reinterpret_cast<const DVmRegs *>(S.slot + M.regs_off)->pad_[0];
+            if (!VM) prev = reinterpret_cast<const DVmRegs *>(S.slot + M.regs_off)->pad_[0];   // (VM: the interpreter wave carries the program's state, vm_stage / vm_dec)
             if (TYPE == ZT_MATCH) {
                 const DCompScal &g = reinterpret_cast<const DCompScal *>(S.slot + M.scal_off)[ci];
                 ma = g.a; mb = g.b; mc = g.c; mlimit = g.limit; mcxt = g.cxt;
@@ -649,7 +650,7 @@ __device__ __forceinline__ void comp_stage(const Stage &S)
         // p[] (DCompScal::pad_[0]) is not written: every input of a model these kernels take is an earlier component, which
         // has predicted this bit before its consumer reads it, so the p[] the lane kernels carry across segments is dead here.
         if (S.active) {
-            if (ci == 0) reinterpret_cast<DVmRegs *>(S.slot + M.regs_off)->pad_[0] = prev;
+            if (!VM && ci == 0) reinterpret_cast<DVmRegs *>(S.slot + M.regs_off)->pad_[0] = prev;
             if (TYPE == ZT_MATCH) {
                 DCompScal &g = reinterpret_cast<DCompScal *>(S.slot + M.scal_off)[ci];
                 g.a = ma; g.b = mb; g.c = mc; g.limit = mlimit; g.cxt = mcxt;
@@ -991,7 +992,7 @@ __device__ __forceinline__ void comp_dec(const DStage &S)
     (void)spec; (void)sa0; (void)sb0; (void)tr_a; (void)tr0; (void)tr1; (void)yprev; (void)trw;
     if constexpr (KEEP) {                                        // (see comp_stage; before the wave's first barrier)
         if (S.active) {
-            prev = reinterpret_cast<const DVmRegs *>(S.slot + M.regs_off)->pad_[0];
+            if (!VM) prev = reinterpret_cast<const DVmRegs *>(S.slot + M.regs_off)->pad_[0];
             if (TYPE == ZT_MATCH) {
                 const DCompScal &g = reinterpret_cast<const DCompScal *>(S.slot + M.scal_off)[ci];
                 ma = g.a; mb = g.b; mc = g.c; mlimit = g.limit;
@@ -1282,7 +1283,7 @@ __device__ __forceinline__ void comp_dec(const DStage &S)
         // nibble's end, and a segment ends on a byte boundary.  MATCH's bit position (DCompScal::cxt) is 0 there and in the slot.
         // p[] is dead for these models (comp_stage).
         if (S.active) {
-            if (ci == 0) reinterpret_cast<DVmRegs *>(S.slot + M.regs_off)->pad_[0] = prev;
+            if (!VM && ci == 0) reinterpret_cast<DVmRegs *>(S.slot + M.regs_off)->pad_[0] = prev;
             if (TYPE == ZT_MATCH) {
                 DCompScal &g = reinterpret_cast<DCompScal *>(S.slot + M.scal_off)[ci];
                 g.a = ma; g.b = mb; g.c = mc; g.limit = mlimit; g.cxt = 0;
@@ -1529,11 +1530,20 @@ __device__ __forceinline__ void vm_bind(zpqvm::Vm &z, const DModel &M, u8 *slot,
 // The interpreter wave of the encoder.  In iteration `it` it runs the program on byte `it` (the PP byte is a byte like any
 // other) and leaves H[i], i < n, as the context of byte it + 1 in component i's ring; component wave i reads it in iteration
 // it + 1 + i.  Component i's ring therefore holds bytes it - i .. it + 1: i + 2 entries.  Returns the block's status.
+// KEEP (block sets, k_vset): M, H and R are in the member's slot already; a b c d f pc come from DVmRegs, where
+// k_rows / k_lanes<..., KEEP, VMH = false> keep them, before the wave's first barrier and go back behind its last.
+template <bool KEEP = false>
 __device__ __forceinline__ i32 vm_stage(const Stage &S, const VCfg &V)
 {
     const DModel &M = *S.M;
     zpqvm::Vm z;
     vm_bind(z, M, S.slot, S.lds + V.hdr_off);
+    if constexpr (KEEP) {
+        if (S.active) {
+            const DVmRegs &g = *reinterpret_cast<const DVmRegs *>(S.slot + M.regs_off);
+            z.a = g.a; z.b = g.b; z.c = g.c; z.d = g.d; z.f = g.f; z.pc = g.pc;
+        }
+    }
     u32 *const ctx = reinterpret_cast<u32 *>(S.lds + V.ctx_off) + S.lane;
     const bool pp = (S.B->flags & ZPQ_FLAG_PP) != 0;
     const u32 total = S.total;
@@ -1549,6 +1559,14 @@ __device__ __forceinline__ i32 vm_stage(const Stage &S, const VCfg &V)
                 ctx[((u32)V.coff[i] + ((it + 1u) & (u32)V.cmask[i])) * BPW] = (u32)i < M.hlen ? z.h[i] : 0u;
         }
         lds_barrier();
+    }
+    if constexpr (KEEP) {
+        // The program ran only while it < the lane's own total: the registers stand at its segment's end (a segment of no
+        // byte leaves them as they were).  M, H and R were written in place.
+        if (S.active) {
+            DVmRegs &g = *reinterpret_cast<DVmRegs *>(S.slot + M.regs_off);
+            g.a = z.a; g.b = z.b; g.c = z.c; g.d = z.d; g.f = z.f; g.pc = z.pc;
+        }
     }
     return status;
 }
@@ -1636,17 +1654,100 @@ __global__ void __launch_bounds__(1024) k_vpipe(const DBatch B, const VCfg V)
     }
 }
 
+// Block sets (ZPQ_SET_VMWAVES): the state hand-over form of k_vpipe, as k_wset is k_gpipe's.  One segment of B.nblocks
+// members per launch; lane l of workgroup w codes entry i = 64 w + l on slot B.slot_map[i]; lanes beyond B.nblocks read
+// no map entry, touch no slot and code nothing.  No rounds, no Predictor.init (k_set_init initialised the set once).  The
+// context rings start at 0 for every segment (Predictor.reset: h[i] = 0); the program's H in the slot is not cleared.  The
+// slot is left in the format of k_rows / k_lanes<..., KEEP, VMH = false>, so calls on a set may alternate between them.
+template <bool BATCH>
+__global__ void __launch_bounds__(1024) k_vset(const DBatch B, const VCfg V)
+{
+    extern __shared__ __align__(16) u8 lds[];
+    const DModel &M = *B.model;
+    const GCfg &cfg = V.g;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    u32 *const misc = reinterpret_cast<u32 *>(lds + L_LINK + (size_t)cfg.ring * BPW * 16);
+    u32 *const s_ctx = reinterpret_cast<u32 *>(lds + V.ctx_off);
+    i32 *const s_stat = reinterpret_cast<i32 *>(lds + V.stat_off);
+    {
+        u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
+        for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
+        u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
+        for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
+        for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
+        u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
+        for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
+        int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
+        for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
+        for (int i = tid; i < M.hdr_len && i < ZPQ_MAX_HDR; i += nthr) lds[V.hdr_off + i] = M.header[i];
+        const int nctx = (V.stat_off - V.ctx_off) / 4;
+        for (int i = tid; i < nctx; i += nthr) s_ctx[i] = 0u;    // byte 0 of the segment is coded under contexts of 0
+        if (tid == 0) *misc = 0u;
+    }
+    __syncthreads();
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = cfg.n;                                         // waves 0 .. n - 1: the components, n: the coder, n + 1: the interpreter
+    const int blk = blockIdx.x * BPW + lane;
+    const bool active = blk < B.nblocks;
+    const int slot_ix = active ? B.slot_map[blk] : 0;
+
+    Stage S;
+    S.B = &B; S.M = &M; S.lds = lds; S.ci = wave; S.lane = lane; S.n = n; S.cfg = &cfg; S.active = active;
+    S.slot = B.slots + (u64)slot_ix * M.slot_bytes;              // (an inactive lane never dereferences it)
+    S.src = active ? B.in + B.in_off[blk] : B.in;
+    S.nin = active ? (u32)(B.in_off[blk + 1] - B.in_off[blk]) : 0u;
+    S.dst = active ? B.out + B.out_off[blk] : B.out;
+    S.cap = active ? (u32)(B.out_off[blk + 1] - B.out_off[blk]) : 0u;
+    S.total = active ? S.nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u) : 0u;
+    if (wave == 0) atomicMax(misc, S.total);
+    __syncthreads();
+    S.iters = *misc + (u32)n;
+    S.hashes = 0;
+    S.busy = 0;
+    S.vctx = s_ctx + (wave < n ? (int)V.coff[wave] : 0) * BPW + lane;
+    S.vmask = wave < n ? (u32)V.cmask[wave] : 0u;
+    u32 opos = 0;
+    if (wave < n) {
+        switch (M.comp[wave].type) {                             // uniform per wave
+        case ZT_CONST: comp_stage<ZT_CONST, BATCH, true, true>(S); break;
+        case ZT_CM: comp_stage<ZT_CM, BATCH, true, true>(S); break;
+        case ZT_ICM: comp_stage<ZT_ICM, BATCH, true, true>(S); break;
+        case ZT_MATCH: comp_stage<ZT_MATCH, BATCH, true, true>(S); break;
+        case ZT_AVG: comp_stage<ZT_AVG, BATCH, true, true>(S); break;
+        case ZT_MIX2: comp_stage<ZT_MIX2, BATCH, true, true>(S); break;
+        case ZT_MIX: comp_stage<ZT_MIX, BATCH, true, true>(S); break;
+        case ZT_ISSE: comp_stage<ZT_ISSE, BATCH, true, true>(S); break;
+        default: comp_stage<ZT_SSE, BATCH, true, true>(S); break;
+        }
+    } else if (wave == n) opos = coder_stage(S);
+    else s_stat[lane] = vm_stage<true>(S, V);
+    __syncthreads();
+    if (wave == n && active) {
+        const i32 vst = s_stat[lane];
+        B.out_len[blk] = opos;
+        B.status[blk] = vst != ZPQ_OK ? vst : (opos > S.cap ? ZPQ_E_OVERFLOW : ZPQ_OK);
+    }
+}
+
 // The interpreter wave of the decoder: it keeps step with the bits (the same barriers as every wave), collects the byte
 // from the decoder wave's bits and, at the byte's end, runs the program for every lane whose block was alive in that byte;
 // H[0 .. n) goes to LDS before the next byte's first barrier, behind which the component waves read it.  A wave of its
 // own rather than the decoder wave: the run then overlaps the decoder wave's output byte, EOF flag and refill and the
 // MATCH wave's search at the byte boundary, and the interpreter's registers stay out of the decoder wave's.
+// KEEP (block sets, k_vsetd): as in vm_stage.
+template <bool KEEP = false>
 __device__ __forceinline__ i32 vm_dec(const DStage &S, const VCfg &V)
 {
     const DModel &M = *S.M;
     u8 *const lds = S.lds;
     zpqvm::Vm z;
     vm_bind(z, M, S.slot, lds + V.hdr_off);
+    if constexpr (KEEP) {                                        // (before the wave's first barrier)
+        if (S.active) {
+            const DVmRegs &g = *reinterpret_cast<const DVmRegs *>(S.slot + M.regs_off);
+            z.a = g.a; z.b = g.b; z.c = g.c; z.d = g.d; z.f = g.f; z.pc = g.pc;
+        }
+    }
     const u32 *const s_y = reinterpret_cast<const u32 *>(lds + D_Y);
     const u32 *const s_alive = reinterpret_cast<const u32 *>(lds + D_ALIVE);
     const u32 *const s_any = reinterpret_cast<const u32 *>(lds + D_ANY);
@@ -1667,6 +1768,14 @@ __device__ __forceinline__ i32 vm_dec(const DStage &S, const VCfg &V)
         if (alive) {                                             // (a block that has ended runs no interpreter)
             if (!zpqvm::vm_run(z, c8 - 256u)) status = ZPQ_E_VMSTEPS;
             for (int i = 0; i < S.n; i++) s_h[i * BPW] = (u32)i < M.hlen ? z.h[i] : 0u;
+        }
+    }
+    if constexpr (KEEP) {
+        // The program ran only for bytes in which the lane's block was alive: the registers stand where the member's segment
+        // ended, whatever the rest of the workgroup went on to decode.
+        if (S.active) {
+            DVmRegs &g = *reinterpret_cast<DVmRegs *>(S.slot + M.regs_off);
+            g.a = z.a; g.b = z.b; g.c = z.c; g.d = z.d; g.f = z.f; g.pc = z.pc;
         }
     }
     return status;
@@ -1736,6 +1845,61 @@ __global__ void __launch_bounds__(1024) k_vdec(const DBatch B, const VCfg V)
         if (wave == n && active && s_stat[lane] != ZPQ_OK) B.status[blk] = s_stat[lane];   // (sticky: ahead of the decoder wave's ZPQ_E_OVERFLOW)
         __syncthreads();
     }
+}
+
+// Block sets (ZPQ_SET_VMWAVES), decoding: as k_vset.  64 lanes per workgroup (ZPQ_GDEC_BPW is not read).
+__global__ void __launch_bounds__(1024) k_vsetd(const DBatch B, const VCfg V)
+{
+    extern __shared__ __align__(16) u8 lds[];
+    const DModel &M = *B.model;
+    const GCfg &cfg = V.g;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    u32 *const s_h = reinterpret_cast<u32 *>(lds + V.ctx_off);
+    i32 *const s_stat = reinterpret_cast<i32 *>(lds + V.stat_off);
+    const int n = cfg.n;                                         // waves 0 .. n - 1: the components, n: the decoder, n + 1: the interpreter
+    {
+        u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
+        for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
+        u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
+        for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
+        for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
+        u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
+        for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
+        int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
+        for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
+        for (int i = tid; i < M.hdr_len && i < ZPQ_MAX_HDR; i += nthr) lds[V.hdr_off + i] = M.header[i];
+        for (int i = tid; i < n * BPW; i += nthr) s_h[i] = 0u;   // the segment's first byte is decoded under contexts of 0
+    }
+    __syncthreads();
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int blk = blockIdx.x * BPW + lane;
+    const bool active = blk < B.nblocks;
+    const int slot_ix = active ? B.slot_map[blk] : 0;
+    DStage S;
+    S.B = &B; S.M = &M; S.lds = lds; S.cfg = &cfg; S.ci = wave; S.lane = lane; S.n = n; S.active = active; S.blk = blk;
+    S.slot = B.slots + (u64)slot_ix * M.slot_bytes;              // (an inactive lane never dereferences it)
+    S.src = active ? B.in + B.in_off[blk] : B.in;
+    S.nin = active ? (u32)(B.in_off[blk + 1] - B.in_off[blk]) : 0u;
+    S.dst = active ? B.out + B.out_off[blk] : B.out;
+    S.cap = active ? (u32)(B.out_off[blk + 1] - B.out_off[blk]) : 0u;
+    S.prof[0] = S.prof[1] = S.prof[2] = S.prof[3] = 0;
+    S.vctx = s_h + (wave < n ? wave : 0) * BPW + lane;
+    if (wave < n) {
+        switch (M.comp[wave].type) {                             // uniform per wave
+        case ZT_CONST: comp_dec<ZT_CONST, true, true>(S); break;
+        case ZT_CM: comp_dec<ZT_CM, true, true>(S); break;
+        case ZT_ICM: comp_dec<ZT_ICM, true, true>(S); break;
+        case ZT_MATCH: comp_dec<ZT_MATCH, true, true>(S); break;
+        case ZT_AVG: comp_dec<ZT_AVG, true, true>(S); break;
+        case ZT_MIX2: comp_dec<ZT_MIX2, true, true>(S); break;
+        case ZT_MIX: comp_dec<ZT_MIX, true, true>(S); break;
+        case ZT_ISSE: comp_dec<ZT_ISSE, true, true>(S); break;
+        default: comp_dec<ZT_SSE, true, true>(S); break;
+        }
+    } else if (wave == n) coder_dec(S);
+    else s_stat[lane] = vm_dec<true>(S, V);
+    __syncthreads();
+    if (wave == n && active && s_stat[lane] != ZPQ_OK) B.status[blk] = s_stat[lane];   // (ahead of the decoder wave's ZPQ_E_OVERFLOW)
 }
 
 }  // namespace zpqg
@@ -2067,5 +2231,37 @@ extern "C" int zpq_launch_vdec(const DBatch *B, const DModel *hostM, int nslots,
     const int nwg = (nslots + bpw - 1) / bpw;
     (void)hipFuncSetAttribute((const void *)zpqg::k_vdec, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipLaunchKernelGGL(zpqg::k_vdec, dim3(nwg), dim3(64 * (V.g.n + 2)), dlds, stream, *B, V);
+    return ZPQ_OK;
+}
+
+// ---- block sets on the interpreter-wave kernels (ZPQ_SET_VMWAVES): one segment of B->nblocks members in one launch of
+// k_vset / k_vsetd, entry i on slot B->slot_map[i].  The caller has checked the envelope (zpq_blockset_vmwaves_applies) and
+// this call's ZPQ_ENC_GPIPE / ZPQ_DEC_GPIPE; ZPQ_GPIPE_BATCH=0 selects the bit-serial encoder stages as for k_vpipe; the
+// decoder always runs 64 lanes per workgroup (ZPQ_GDEC_BPW is not read, as in zpq_launch_wset).
+extern "C" int zpq_launch_vset(const DBatch *B, const DModel *hostM, int decode, hipStream_t stream, const char **name)
+{
+    zpqg::VCfg V;
+    size_t lds = 0, dlds = 0;
+    if (!vpipe_cfg(hostM, &V, &lds, &dlds)) return ZPQ_E_INTERNAL;
+    if (B->nblocks < 1 || B->nslots != B->nblocks || !B->slot_map) return ZPQ_E_INTERNAL;   // (no identity map: the slots are the set's)
+    V.g.bpw = zpqg::BPW;
+    const dim3 g((B->nblocks + zpqg::BPW - 1) / zpqg::BPW), t(64 * (V.g.n + 2));
+    if (decode) {
+        vpipe_offsets(&V, dlds, V.g.n * zpqg::BPW, hostM->hdr_len);
+        (void)hipFuncSetAttribute((const void *)zpqg::k_vsetd, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipLaunchKernelGGL(zpqg::k_vsetd, g, t, dlds, stream, *B, V);
+        *name = "k_vsetd<decode>";
+        return ZPQ_OK;
+    }
+    vpipe_offsets(&V, lds, (int)(V.coff[V.g.n - 1] + V.cmask[V.g.n - 1] + 1) * zpqg::BPW, hostM->hdr_len);
+    const char *ev = getenv("ZPQ_GPIPE_BATCH");
+    if (ev && atoi(ev) == 0) {
+        (void)hipFuncSetAttribute((const void *)zpqg::k_vset<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipLaunchKernelGGL(zpqg::k_vset<false>, g, t, lds, stream, *B, V);
+    } else {
+        (void)hipFuncSetAttribute((const void *)zpqg::k_vset<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipLaunchKernelGGL(zpqg::k_vset<true>, g, t, lds, stream, *B, V);
+    }
+    *name = "k_vset<encode>";
     return ZPQ_OK;
 }
