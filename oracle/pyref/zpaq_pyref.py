@@ -12,6 +12,14 @@ V semantics made explicit: `int` = 32-bit two's complement with wrap-around
 
 M32 = 0xFFFFFFFF
 
+# Inline constants of the reference that sit on a numeric edge, named so that a test can read them and move them by one
+# (tests/numeric_edges.py); the arithmetic that uses them is unchanged.
+MIX2_W_MIN, MIX2_W_MAX = 0, 65535      # predictor.v: the MIX2 weight's clamp in update
+MATCH_MAX_LEN = 255                    # predictor.v: the longest match length, by increment and in the recovery loop
+MATCH_RESET_LEN = 0                    # predictor.v: the length after a mispredicted bit
+SSE_PQ_MIN, SSE_PQ_MAX = 0, 1983       # predictor.v: the clamp of the SSE's interpolation position
+LOW_REPAIR = 1                         # encoder.v / decoder.v: what replaces a low of 0 after a byte is shifted out
+
 
 def u32(x):
     return x & M32
@@ -658,10 +666,10 @@ class Predictor:
                 pq = 992
                 if j < n:
                     pq = p[j] + 992
-                if pq < 0:
-                    pq = 0
-                if pq > 1983:
-                    pq = 1983
+                if pq < SSE_PQ_MIN:
+                    pq = SSE_PQ_MIN
+                if pq > SSE_PQ_MAX:
+                    pq = SSE_PQ_MAX
                 wt = pq & 63
                 pq >>= 6
                 idx = i32(i32(cr.cxt) + pq)
@@ -698,7 +706,7 @@ class Predictor:
                 cr.cm[cr.cxt] = u32(i32(v) + ((y * 32767 - (v >> 8)) >> 2))
             elif t == 4:
                 if cr.c != y:
-                    cr.a = 0
+                    cr.a = MATCH_RESET_LEN
                 mask = len(cr.ht) - 1
                 idx = cr.limit & mask
                 cr.ht[idx] = u8((cr.ht[idx] << 1) | y)
@@ -712,13 +720,13 @@ class Predictor:
                     if cr.a == 0:
                         cr.b = i32(cr.limit - i32(cr.cm[ci]))
                         if (cr.b & mask) != 0:
-                            while cr.a < 255:
+                            while cr.a < MATCH_MAX_LEN:
                                 i1 = (cr.limit - cr.a - 1) & mask
                                 i2 = (cr.limit - cr.a - cr.b - 1) & mask
                                 if cr.ht[i1] != cr.ht[i2]:
                                     break
                                 cr.a += 1
-                    elif cr.a < 255:
+                    elif cr.a < MATCH_MAX_LEN:
                         cr.a += 1
                     cr.cm[ci] = u32(cr.limit)
             elif t == 6:
@@ -727,10 +735,10 @@ class Predictor:
                 if j < n and k < n:
                     w = cr.a16[cr.cxt]
                     w += i32(i32(err * (p[j] - p[k])) + (1 << 12)) >> 13
-                    if w < 0:
-                        w = 0
-                    if w > 65535:
-                        w = 65535
+                    if w < MIX2_W_MIN:
+                        w = MIX2_W_MIN
+                    if w > MIX2_W_MAX:
+                        w = MIX2_W_MAX
                     cr.a16[cr.cxt] = w
             elif t == 7:
                 jj, m, rate = cr.b, cr.limit, cr.ht[0]
@@ -798,7 +806,7 @@ class Encoder:  # encoder.v
             self.low = u32(self.low << 8)
             self.high = u32(self.high << 8) | 0xFF
             if self.low == 0:
-                self.low = 1
+                self.low = LOW_REPAIR
 
     def compress(self, c):  # encoder.v:93-120
         if c == -1:
@@ -854,7 +862,7 @@ class Decoder:  # decoder.v
             self.low = u32(self.low << 8)
             self.high = u32(self.high << 8) | 0xFF
             if self.low == 0:
-                self.low = 1
+                self.low = LOW_REPAIR
             self._shift()
         return y
 
