@@ -281,9 +281,9 @@ int zpq_block_decode_segment(zpq_block *, const uint8_t *in, size_t n, uint32_t 
  *                         hand-over form of each), one launch per round whatever the number of members.  Honoured when
  *                         zpq_blockset_lanes_applies(model): no chain kernel takes it and it has at most 64 components.
  *                         Otherwise it decides nothing.  The capacity of such a set is bounded by memory alone.  It keeps
- *                         p[], the last bit's predictions, across segments as the reference does; the lane-0 kernel
- *                         starts every segment with p[] = 0, which differs only for a component whose input index is not
- *                         below its own.  The environment variable ZPQ_SET_LANES=1 makes the request for every set the
+ *                         p[], the last bit's predictions, across segments as the reference does (a component whose
+ *                         input index is not below its own reads them at a segment's first bit), and so does the lane-0
+ *                         kernel: the same bytes on either route.  ZPQ_SET_LANES=1 in the environment makes the request for every set the
  *                         process creates, ZPQ_SET_LANES=0 withdraws it (anything but a leading 0 / 1 decides nothing).
  *   ZPQ_SET_PIPE          a request: run the ENCODE calls of a chain-model set on the wave-pipelined encoder (k_pipe, a state
  *                         hand-over form of it) instead of the lane-per-component one (k_chain).  Honoured when

@@ -114,8 +114,7 @@ def test_the_gpu_cases_tell_a_kept_p_from_a_zeroed_one(no_knobs, what):
     the oracle.  In fwd_isse and fwd_avg a component reads a LATER component's prediction and feeds the coded one: the
     first bit of a segment is coded with what was predicted for the last bit of the segment before.  On members that
     test_gpu_set_lanes.py::test_parity codes for these models, the Python reference with p[] zeroed between segments
-    writes other bytes than the oracle does: a set that dropped p[] would fail those cases.  (k_generic's sets do start
-    every segment from p[] = 0: DESIGN.md 4.4.)"""
+    writes other bytes than the oracle does: a set that dropped p[] would fail those cases."""
     import oracle_lib as O
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "pyref"))
     import zpaq_pyref as P

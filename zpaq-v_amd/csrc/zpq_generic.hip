@@ -479,7 +479,7 @@ __global__ void __launch_bounds__(64) k_generic(const DBatch B)
         for (int i = lane; i < M.n; i += 64) {
             S.cs[i] = gs[i];
             S.h[i] = 0;                              // Predictor.reset() (predictor.v:827-833)
-            S.p[i] = 0;
+            S.p[i] = (B.flags & ZB_KEEP_STATE) ? (i32)gs[i].pad_[0] : 0;   // (reset() leaves p[] alone: below)
             S.row[i] = 0;
             S.cxt[i] = 0;
         }
@@ -489,8 +489,13 @@ __global__ void __launch_bounds__(64) k_generic(const DBatch B)
         P.M = &M; P.slot = slot; P.S = &S; P.n = M.n;
         P.T.squash = B.squash; P.T.stretch = B.stretch; P.T.dt2k = B.dt2k; P.T.dt = B.dt; P.T.ns = B.ns;
         P.c8 = 1; P.hmap4 = 1;
-        // p[] persists across segments in the reference (stale-p quirk Q13) but every
-        // shipped use predicts before reading; slots keep it zeroed like a fresh Predictor.
+        // p[] persists across segments in the reference (stale-p quirk Q13): a component whose input index is not below
+        // its own reads, at a segment's first bit, what was predicted for the last bit of the segment before.  It is kept
+        // in DCompScal::pad_[0], the word and the i32-in-u32 form of k_rows / k_lanes<..., KEEP> (zpq_lanes.hip), stored at
+        // every segment's end (the first one's and a replay's included) and loaded under ZB_KEEP_STATE; a fresh slot is
+        // zeroed and reads as p[] = 0, a fresh Predictor's.  The only other meaning that word has is k_chain<..., KEEP>'s
+        // scratch for a lane without a MIX2 (zpq_chain.hip), on the slots of a chain-model set, which this kernel never
+        // runs on (set_segments: such a set is coded by the chain kernels alone) -- and no chain model reads p[] forward.
         Vm z;
         z.a = gr->a; z.b = gr->b; z.c = gr->c; z.d = gr->d; z.f = gr->f; z.pc = gr->pc;
         z.m = slot + M.m_off; z.mlen = M.mlen;
@@ -585,7 +590,10 @@ __global__ void __launch_bounds__(64) k_generic(const DBatch B)
         __syncthreads();
         // persist what outlives a segment
         if (lane == 0) { gr->a = z.a; gr->b = z.b; gr->c = z.c; gr->d = z.d; gr->f = z.f; gr->pc = z.pc; }
-        for (int i = lane; i < M.n; i += 64) gs[i] = S.cs[i];
+        for (int i = lane; i < M.n; i += 64) {
+            S.cs[i].pad_[0] = (u32)S.p[i];
+            gs[i] = S.cs[i];
+        }
         __syncthreads();
     }
 }
