@@ -39,3 +39,22 @@ def test_specialised_kernels_use_no_scratch(zpq):
     for name, r in t.items():
         if "k_lanes" in name and name.endswith("Lb1EEEv6DBatchNS_4LCfgE"):   # the hash-chain instantiation (no interpreter)
             assert r["scratch"] == 0, (name, r)
+
+
+def test_wave_family_resources(zpq):
+    """The twelve kernels of zpq_gpipe.hip are built from shared pieces: a piece that costs one of them a register shows
+    here, not in a parity test.  All run up to sixteen waves of one workgroup, four per SIMD: 128 VGPRs at most.  Scratch
+    ceilings are what the kernels had when the pieces were shared: two registers spilled once per byte in
+    k_vpipe<batched>, one in k_vdec (the interpreter wave's), none elsewhere."""
+    zpq.lib()
+    from kernel_stats import kernel_table
+    t = kernel_table()
+    scratch = {"k_wsetdE": 0, "k_vdecE": 8, "k_vsetdE": 0, "k_wsetILb1E": 0, "k_wsetILb0E": 0,       # (k_gdec and the two k_gpipe: above)
+               "k_vpipeILb1E": 16, "k_vpipeILb0E": 0, "k_vsetILb1E": 0, "k_vsetILb0E": 0}
+    family = {k: v for k, v in t.items() if any(s in k for s in ("k_gpipe", "k_gdec", "k_wset", "k_vpipe", "k_vdec", "k_vset"))}
+    assert len(family) == 12, sorted(family)
+    for key, ceiling in scratch.items():
+        found = [k for k in family if key in k]
+        assert len(found) == 1, (key, found)
+        r = family[found[0]]
+        assert r["vgpr"] <= 128 and r["scratch"] <= ceiling, (found[0], r)

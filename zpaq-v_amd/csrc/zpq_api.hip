@@ -1197,25 +1197,6 @@ extern "C" int zpq_block_decode_segment(zpq_block *b, const uint8_t *in, size_t 
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 // ------------------------------------------------------------------ N blocks, many segments
-// Predictor.init's fill of one chain-model slot, in the form k_chain<..., KEEP> loads: ICM cm[] = cminit, ISSE weight pairs,
-// MIX2 weights 32768 (predictor.v:366-368,396,443-445); everything else was zeroed before.  One workgroup per slot.
-__global__ void __launch_bounds__(256) k_set_fill(const DModel *Mp, const uint32_t *img, uint8_t *slots)
-{
-    const DModel &M = *Mp;
-    uint8_t *slot = slots + (uint64_t)blockIdx.x * M.slot_bytes;
-    for (int ci = 0; ci < M.n; ci++) {
-        const DComp &c = M.comp[ci];
-        if (c.cm_len && c.cm_fill == ZF_PATTERN) {
-            uint32_t *cm = reinterpret_cast<uint32_t *>(slot + c.cm_off);
-            for (uint32_t i = threadIdx.x; i < c.cm_len; i += 256) cm[i] = img[c.cm_fill_val + i % c.cm_pat_len];
-        }
-        if (c.a16_len && c.a16_fill) {
-            uint16_t *a16 = reinterpret_cast<uint16_t *>(slot + c.a16_off);
-            for (uint32_t i = threadIdx.x; i < c.a16_len; i += 256) a16[i] = (uint16_t)c.a16_fill;
-        }
-    }
-}
-
 // the layout a set of this model gets: the line store wherever a table is larger than a store sized for max_member_bytes
 // (the slots are the set's for its whole life, so the smaller slot always pays), unless ZPQ_SPARSE_MODE=never
 static bool set_layout(const zpq_ctx *c, const zpq_model *m, uint64_t max_member_bytes, DModel *layout, uint32_t *sp)
@@ -1334,18 +1315,12 @@ extern "C" int zpq_blockset_create_ex(zpq_ctx *c, const zpq_model *m, int nmembe
         if (hipMalloc((void **)&s->slots, s->bytes) != hipSuccess) { (void)hipGetLastError(); delete s; return ZPQ_E_NOMEM; }
     }
     int rc = ZPQ_OK;
-    if (s->chain) {
+    if (s->chain || lanes) {
+        // Predictor.init + ZPAQL.clear of every member now: each launch on the set is KEEP, the first segment's included.
+        // (A chain model -- ICM, ISSE, MIX2 -- has its zeroed part, ICM cm[] = cminit, ISSE weight pairs and MIX2 weights
+        // 32768 to set, predictor.v:366-368,396,443-445: k_set_init's fill, whose ZF_CONST and MATCH cases find nothing.)
         DevModel dm;
         rc = get_dev_model(c, m, s->layout, s->sp, &dm);
-        if (rc == ZPQ_OK && hipMemset2DAsync(s->slots, s->layout.slot_bytes, 0, s->layout.zero_bytes, (size_t)nmembers, c->stream) != hipSuccess) rc = ZPQ_E_NODEVICE;
-        if (rc == ZPQ_OK) {
-            hipLaunchKernelGGL(k_set_fill, dim3(nmembers), dim3(256), 0, c->stream, (const DModel *)dm.d_model, (const uint32_t *)dm.d_img, s->slots);
-            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = ZPQ_E_NODEVICE;
-        }
-    } else if (lanes) {
-        // Predictor.init + ZPAQL.clear of every member now: each launch on the set is KEEP, the first segment's included
-        DevModel dm;
-        rc = get_dev_model(c, m, s->layout, 0, &dm);
         if (rc == ZPQ_OK) rc = zpq_launch_lanes_set_init(dm.d_model, dm.d_img, s->slots, nmembers, c->stream);
         if (rc == ZPQ_OK && (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) rc = ZPQ_E_NODEVICE;
     }

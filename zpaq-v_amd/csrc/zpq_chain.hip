@@ -38,6 +38,7 @@
 #include "zpq_vm.h"
 #include "zpq_host.h"
 #include "zpq_chain_cfg.h"
+#include "zpq_dev.h"
 
 // Measured on MI355X: the pipelined step wins for encode, for decode the step with
 // fewer instructions wins (both-candidate speculation was slower every time it was tried).
@@ -46,20 +47,11 @@ constexpr bool CHAIN_SPEC_ENC = true, CHAIN_SPEC_DEC = false;
 
 namespace zpqc {
 
-__device__ __forceinline__ i32 wadd(i32 a, i32 b) { return (i32)((u32)a + (u32)b); }
-__device__ __forceinline__ i32 wmul(i32 a, i32 b) { return (i32)((u32)a * (u32)b); }
+using namespace zpqdev;
 // The MIX2's products in the specialised decoders: a weight (<= 65536) or an error term (|err| < 2^15, rate < 2^8, |em| < 2^18) times a
 // prediction or a difference of two (|p| <= 2048, |pj - pk| < 2^12): every operand fits 24 signed bits and no product leaves 32 -- the
 // full-rate 24-bit multiply is exact where V's wrapping 32-bit multiply (a quarter-rate v_mul_lo_u32 / v_mad_u64_u32) is.
 __device__ __forceinline__ i32 mul24x(i32 a, i32 b) { return __mul24(a, b); }
-__device__ __forceinline__ i32 clamp2k(i32 x) { return min(max(x, -2048), 2047); }
-// (u64(range) * p16) >> 16 for p16 < 2^16 (encoder.v:60-61, decoder.v:86-87) without the 64-bit multiply:
-// range = hi * 2^16 + lo  =>  hi * p16 + ((lo * p16) >> 16), both products of 16-bit operands (two full-rate v_mul_u32_u24)
-__device__ __forceinline__ uint32_t mul_shr16(uint32_t range, uint32_t p16)
-{
-    return (uint32_t)__umul24(range >> 16, p16) + ((uint32_t)__umul24(range & 0xFFFFu, p16) >> 16);   // (__umul24 returns int)
-}
-__device__ __forceinline__ i32 clamp512k(i32 x) { return min(max(x, -262144), 262143); }
 
 // value of lane (li-1) of the same 16-lane row; lane 0 of a row gets `self`
 __device__ __forceinline__ i32 row_shr1(i32 self)

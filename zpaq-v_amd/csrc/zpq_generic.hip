@@ -22,6 +22,7 @@
 #include "../../include/zpaq_hip.h"
 #include "zpq_common.h"
 #include "zpq_vm.h"
+#include "zpq_dev.h"
 
 namespace zpqg {
 
@@ -31,9 +32,7 @@ typedef uint64_t u64;
 typedef uint8_t u8;
 typedef uint16_t u16;
 
-__device__ __forceinline__ i32 wadd(i32 a, i32 b) { return (i32)((u32)a + (u32)b); }
-__device__ __forceinline__ i32 wsub(i32 a, i32 b) { return (i32)((u32)a - (u32)b); }
-__device__ __forceinline__ i32 wmul(i32 a, i32 b) { return (i32)((u32)a * (u32)b); }
+using namespace zpqdev;
 
 constexpr int GEN_LDS_COMP = 32;   // component descriptors cached in LDS (the rest are read from HBM)
 
@@ -78,8 +77,6 @@ __device__ __forceinline__ i32 stretch(const Tab &T, i32 p)
     if (p >= 32768) p = 32767;
     return T.stretch[p];
 }
-__device__ __forceinline__ i32 clamp2k(i32 x) { return x < -2048 ? -2048 : (x > 2047 ? 2047 : x); }
-__device__ __forceinline__ i32 clamp512k(i32 x) { return x < -262144 ? -262144 : (x > 262143 ? 262143 : x); }
 // statetable.v:75-84 (state is always a byte here)
 __device__ __forceinline__ u8 ns_next(const Tab &T, u32 s, i32 y) { return T.ns[(s & 255) * 4 + y]; }
 
@@ -411,34 +408,10 @@ __device__ __forceinline__ i32 dec_bit(Dec &d, u32 p16)
 __device__ void init_slot(const DBatch &B, u8 *slot, const int lane)
 {
     const DModel &M = *B.model;
-    uint4 *z4 = reinterpret_cast<uint4 *>(slot);
-    const u64 n16 = M.zero_bytes / 16;
-    const uint4 zero = make_uint4(0, 0, 0, 0);
-    for (u64 i = lane; i < n16; i += 64) z4[i] = zero;
+    slot_zero(M, slot, lane, 64);
     __syncthreads();
-    for (i32 ci = 0; ci < M.n; ci++) {
-        const DComp &c = M.comp[ci];
-        if (c.cm_len && c.cm_fill != ZF_ZERO) {
-            u32 *cm = reinterpret_cast<u32 *>(slot + c.cm_off);
-            if (c.cm_fill == ZF_CONST) {
-                for (u32 i = lane; i < c.cm_len; i += 64) cm[i] = c.cm_fill_val;
-            } else {
-                const u32 *img = B.img + c.cm_fill_val;
-                for (u32 i = lane; i < c.cm_len; i += 64) cm[i] = img[i % c.cm_pat_len];
-            }
-        }
-        if (c.a16_len && c.a16_fill) {
-            u16 *a16 = reinterpret_cast<u16 *>(slot + c.a16_off);
-            for (u32 i = lane; i < c.a16_len; i += 64) a16[i] = (u16)c.a16_fill;
-        }
-        if (c.type == ZT_MATCH && lane == 0) {
-            // Quirk: Predictor.init leaves sizebits/bufbits in cr.a/cr.b (predictor.v:372-373),
-            // which predict/update then read as the initial match length and offset (:566-572).
-            DCompScal *gs = reinterpret_cast<DCompScal *>(slot + M.scal_off);
-            gs[ci].a = c.a;
-            gs[ci].b = c.b;
-        }
-    }
+    slot_fill(M, B.img, slot, lane, 64);
+    slot_match_init(M, slot, lane, 64);
     __syncthreads();
 }
 

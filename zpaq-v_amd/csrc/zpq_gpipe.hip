@@ -39,6 +39,7 @@
 #include "zpq_common.h"
 #include "zpq_host.h"
 #include "zpq_vm.h"
+#include "zpq_dev.h"
 
 namespace zpqg {
 
@@ -74,16 +75,7 @@ struct GCfg {
     uint8_t dslot[16];           // decoder: an SSE component's row buffer in LDS
 };
 
-__device__ __forceinline__ i32 wadd(i32 a, i32 b) { return (i32)((u32)a + (u32)b); }
-__device__ __forceinline__ i32 wsub(i32 a, i32 b) { return (i32)((u32)a - (u32)b); }
-__device__ __forceinline__ i32 wmul(i32 a, i32 b) { return (i32)((u32)a * (u32)b); }
-__device__ __forceinline__ i32 clamp2k(i32 x) { return min(max(x, -2048), 2047); }
-__device__ __forceinline__ i32 clamp512k(i32 x) { return min(max(x, -262144), 262143); }
-__device__ __forceinline__ uint32_t mul_shr16(uint32_t range, uint32_t p16)   // see zpq_chain.hip
-{
-    return (uint32_t)__umul24(range >> 16, p16) + ((uint32_t)__umul24(range & 0xFFFFu, p16) >> 16);
-}
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+using namespace zpqdev;
 
 // everything a stage needs
 struct Stage {
@@ -708,30 +700,61 @@ __device__ __forceinline__ u32 coder_stage(const Stage &S)
 }
 
 // Predictor.init + ZPAQL.clear for the nact blocks of a workgroup's round (predictor.v:325-470): zero, then the non-zero fills
-__device__ __forceinline__ void init_slots(const DBatch &B, const DModel &M, const int n, const int wg_slot0, const int nact, const int tid, const int nthr)
+__device__ __forceinline__ void init_slots(const DBatch &B, const DModel &M, const int wg_slot0, const int nact, const int tid, const int nthr)
 {
-    const u64 n16 = M.zero_bytes / 16;
-    const uint4 zero = make_uint4(0, 0, 0, 0);
-    for (int b = 0; b < nact; b++) {
-        uint4 *z4 = reinterpret_cast<uint4 *>(B.slots + (u64)(wg_slot0 + b) * M.slot_bytes);
-        for (u64 i = tid; i < n16; i += nthr) z4[i] = zero;
-    }
+    for (int b = 0; b < nact; b++) slot_zero(M, B.slots + (u64)(wg_slot0 + b) * M.slot_bytes, tid, nthr);
     __syncthreads();
-    for (int b = 0; b < nact; b++) {
-        u8 *sl = B.slots + (u64)(wg_slot0 + b) * M.slot_bytes;
-        for (int c = 0; c < n; c++) {
-            const DComp &cc = M.comp[c];
-            if (cc.cm_len && cc.cm_fill != ZF_ZERO) {
-                u32 *t = reinterpret_cast<u32 *>(sl + cc.cm_off);
-                if (cc.cm_fill == ZF_CONST) { for (u32 i = tid; i < cc.cm_len; i += nthr) t[i] = cc.cm_fill_val; }
-                else { const u32 *img = B.img + cc.cm_fill_val; for (u32 i = tid; i < cc.cm_len; i += nthr) t[i] = img[i % cc.cm_pat_len]; }
-            }
-            if (cc.a16_len && cc.a16_fill) {
-                u16 *t = reinterpret_cast<u16 *>(sl + cc.a16_off);
-                for (u32 i = tid; i < cc.a16_len; i += nthr) t[i] = (u16)cc.a16_fill;
-            }
-        }
-    }
+    for (int b = 0; b < nact; b++) slot_fill(M, B.img, B.slots + (u64)(wg_slot0 + b) * M.slot_bytes, tid, nthr);
+}
+
+// ---- what the kernels of this file share, stated once
+// the read-only tables, from HBM into LDS: every kernel's first step (k_vpipe & co. put the header behind them)
+__device__ __forceinline__ void load_tables(const DBatch &B, u8 *lds, const int tid, const int nthr)
+{
+    u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
+    for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
+    u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
+    for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
+    for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
+    u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
+    for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
+    int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
+    for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
+}
+
+// A component wave's byte loop by the component's type (uniform per wave): STAGE<TYPE, ...>(S), comp_stage or comp_dec.
+// A macro, so that the switch stands in the kernel as if written there: as a function template taking S it cost
+// k_vpipe<batched>, which sits at 128 VGPRs with two registers spilled, another 16 bytes of scratch.
+#define ZPG_BY_TYPE(type, S, STAGE, ...)                  \
+    do switch (type) {                                    \
+    case ZT_CONST: STAGE<ZT_CONST, __VA_ARGS__>(S); break; \
+    case ZT_CM: STAGE<ZT_CM, __VA_ARGS__>(S); break;       \
+    case ZT_ICM: STAGE<ZT_ICM, __VA_ARGS__>(S); break;     \
+    case ZT_MATCH: STAGE<ZT_MATCH, __VA_ARGS__>(S); break; \
+    case ZT_AVG: STAGE<ZT_AVG, __VA_ARGS__>(S); break;     \
+    case ZT_MIX2: STAGE<ZT_MIX2, __VA_ARGS__>(S); break;   \
+    case ZT_MIX: STAGE<ZT_MIX, __VA_ARGS__>(S); break;     \
+    case ZT_ISSE: STAGE<ZT_ISSE, __VA_ARGS__>(S); break;   \
+    default: STAGE<ZT_SSE, __VA_ARGS__>(S); break;         \
+    } while (0)
+
+// a lane's input and output ranges, of a Stage or a DStage (on: the kernel's own flag that the lane codes a block).  A macro, so
+// that the four selects stand in the kernel as if written there: as a function the binding is simplified on its own before it is
+// inlined, into one branch where the text in place takes four, and the set kernels' byte loops then lie elsewhere in their code
+// (k_vset<batched> 1.5 % slower, R16)
+#define ZPG_BIND_IO(S, B, blk, on)                                                \
+    do {                                                                          \
+        (S).src = (on) ? (B).in + (B).in_off[blk] : (B).in;                       \
+        (S).nin = (on) ? (u32)((B).in_off[(blk) + 1] - (B).in_off[blk]) : 0u;     \
+        (S).dst = (on) ? (B).out + (B).out_off[blk] : (B).out;                    \
+        (S).cap = (on) ? (u32)((B).out_off[(blk) + 1] - (B).out_off[blk]) : 0u;   \
+    } while (0)
+
+// an encoded block's length and status; vst: the interpreter wave's status, sticky ahead of ZPQ_E_OVERFLOW
+__device__ __forceinline__ void put_result(const DBatch &B, const int blk, const u32 opos, const u32 cap, const i32 vst = ZPQ_OK)
+{
+    B.out_len[blk] = opos;
+    B.status[blk] = vst != ZPQ_OK ? vst : (opos > cap ? ZPQ_E_OVERFLOW : ZPQ_OK);
 }
 
 template <bool BATCH>
@@ -740,17 +763,7 @@ __global__ void __launch_bounds__(1024) k_gpipe(const DBatch B, const GCfg cfg)
     extern __shared__ __align__(16) u8 lds[];
     const DModel &M = *B.model;
     const int tid = threadIdx.x, nthr = blockDim.x;
-    {
-        u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
-        for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
-        u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
-        for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
-        for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
-        u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
-        for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
-        int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
-        for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
-    }
+    load_tables(B, lds, tid, nthr);
     __syncthreads();
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform, and known to the compiler as such: component constants in SGPRs, scalar branches)
     const int n = cfg.n;
@@ -766,7 +779,7 @@ __global__ void __launch_bounds__(1024) k_gpipe(const DBatch B, const GCfg cfg)
         const int blk = base + lane;
         const bool active = lane_on && blk < B.nblocks;
         const int nact = min(wg_slots, B.nblocks - base);
-        init_slots(B, M, n, wg_slot0, nact, tid, nthr);
+        init_slots(B, M, wg_slot0, nact, tid, nthr);
         if (tid == 0) *misc = 0u;
         __threadfence();
         __syncthreads();
@@ -774,11 +787,8 @@ __global__ void __launch_bounds__(1024) k_gpipe(const DBatch B, const GCfg cfg)
         Stage S;
         S.B = &B; S.M = &M; S.lds = lds; S.ci = wave; S.lane = lane; S.n = n; S.cfg = &cfg; S.active = active;
         S.slot = slot;
-        S.src = active ? B.in + B.in_off[blk] : B.in;
-        S.nin = active ? (u32)(B.in_off[blk + 1] - B.in_off[blk]) : 0u;
-        S.dst = active ? B.out + B.out_off[blk] : B.out;
-        S.cap = active ? (u32)(B.out_off[blk + 1] - B.out_off[blk]) : 0u;
-        S.total = active ? S.nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u) : 0u;
+        ZPG_BIND_IO(S, B, blk, active);
+        S.total = active ? S.nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u) : 0u;   // the bytes it codes, the PP byte included
         if (wave == 0) atomicMax(misc, S.total);
         __syncthreads();
         S.iters = *misc + (u32)n;
@@ -788,23 +798,10 @@ __global__ void __launch_bounds__(1024) k_gpipe(const DBatch B, const GCfg cfg)
         const u64 t_all = __builtin_readcyclecounter();
 #endif
         if (wave < n) {
-            switch (M.comp[wave].type) {                         // uniform per wave
-            case ZT_CONST: comp_stage<ZT_CONST, BATCH>(S); break;
-            case ZT_CM: comp_stage<ZT_CM, BATCH>(S); break;
-            case ZT_ICM: comp_stage<ZT_ICM, BATCH>(S); break;
-            case ZT_MATCH: comp_stage<ZT_MATCH, BATCH>(S); break;
-            case ZT_AVG: comp_stage<ZT_AVG, BATCH>(S); break;
-            case ZT_MIX2: comp_stage<ZT_MIX2, BATCH>(S); break;
-            case ZT_MIX: comp_stage<ZT_MIX, BATCH>(S); break;
-            case ZT_ISSE: comp_stage<ZT_ISSE, BATCH>(S); break;
-            default: comp_stage<ZT_SSE, BATCH>(S); break;
-            }
+            ZPG_BY_TYPE(M.comp[wave].type, S, comp_stage, BATCH, false, false);
         } else {
             const u32 opos = coder_stage(S);
-            if (active) {
-                B.out_len[blk] = opos;
-                B.status[blk] = opos > S.cap ? ZPQ_E_OVERFLOW : ZPQ_OK;
-            }
+            if (active) put_result(B, blk, opos, S.cap);
         }
 #ifdef ZPG_PROF
         if (blockIdx.x == 0 && lane == 0 && wave < n)
@@ -826,17 +823,7 @@ __global__ void __launch_bounds__(1024) k_wset(const DBatch B, const GCfg cfg)
     extern __shared__ __align__(16) u8 lds[];
     const DModel &M = *B.model;
     const int tid = threadIdx.x, nthr = blockDim.x;
-    {
-        u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
-        for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
-        u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
-        for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
-        for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
-        u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
-        for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
-        int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
-        for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
-    }
+    load_tables(B, lds, tid, nthr);
     u32 *const misc = reinterpret_cast<u32 *>(lds + L_LINK + (size_t)cfg.ring * BPW * 16);
     if (tid == 0) *misc = 0u;
     __syncthreads();
@@ -849,34 +836,18 @@ __global__ void __launch_bounds__(1024) k_wset(const DBatch B, const GCfg cfg)
     Stage S;
     S.B = &B; S.M = &M; S.lds = lds; S.ci = wave; S.lane = lane; S.n = n; S.cfg = &cfg; S.active = active;
     S.slot = B.slots + (u64)slot_ix * M.slot_bytes;              // (an inactive lane never dereferences it)
-    S.src = active ? B.in + B.in_off[blk] : B.in;
-    S.nin = active ? (u32)(B.in_off[blk + 1] - B.in_off[blk]) : 0u;
-    S.dst = active ? B.out + B.out_off[blk] : B.out;
-    S.cap = active ? (u32)(B.out_off[blk + 1] - B.out_off[blk]) : 0u;
-    S.total = active ? S.nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u) : 0u;
+    ZPG_BIND_IO(S, B, blk, active);
+    S.total = active ? S.nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u) : 0u;   // the bytes it codes, the PP byte included
     if (wave == 0) atomicMax(misc, S.total);
     __syncthreads();
     S.iters = *misc + (u32)n;
     S.hashes = cfg.hashes;
     S.busy = 0;
     if (wave < n) {
-        switch (M.comp[wave].type) {                             // uniform per wave
-        case ZT_CONST: comp_stage<ZT_CONST, BATCH, false, true>(S); break;
-        case ZT_CM: comp_stage<ZT_CM, BATCH, false, true>(S); break;
-        case ZT_ICM: comp_stage<ZT_ICM, BATCH, false, true>(S); break;
-        case ZT_MATCH: comp_stage<ZT_MATCH, BATCH, false, true>(S); break;
-        case ZT_AVG: comp_stage<ZT_AVG, BATCH, false, true>(S); break;
-        case ZT_MIX2: comp_stage<ZT_MIX2, BATCH, false, true>(S); break;
-        case ZT_MIX: comp_stage<ZT_MIX, BATCH, false, true>(S); break;
-        case ZT_ISSE: comp_stage<ZT_ISSE, BATCH, false, true>(S); break;
-        default: comp_stage<ZT_SSE, BATCH, false, true>(S); break;
-        }
+        ZPG_BY_TYPE(M.comp[wave].type, S, comp_stage, BATCH, false, true);
     } else {
         const u32 opos = coder_stage(S);
-        if (active) {
-            B.out_len[blk] = opos;
-            B.status[blk] = opos > S.cap ? ZPQ_E_OVERFLOW : ZPQ_OK;
-        }
+        if (active) put_result(B, blk, opos, S.cap);
     }
 }
 
@@ -1398,17 +1369,7 @@ __global__ void __launch_bounds__(1024) k_gdec(const DBatch B, const GCfg cfg)
     extern __shared__ __align__(16) u8 lds[];
     const DModel &M = *B.model;
     const int tid = threadIdx.x, nthr = blockDim.x;
-    {
-        u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
-        for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
-        u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
-        for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
-        for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
-        u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
-        for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
-        int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
-        for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
-    }
+    load_tables(B, lds, tid, nthr);
     __syncthreads();
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform, and known to the compiler as such: component constants in SGPRs, scalar branches)
     const int n = cfg.n;
@@ -1423,28 +1384,15 @@ __global__ void __launch_bounds__(1024) k_gdec(const DBatch B, const GCfg cfg)
         const int blk = base + lane;
         const bool active = lane_on && blk < B.nblocks;
         const int nact = min(wg_slots, B.nblocks - base);
-        init_slots(B, M, n, wg_slot0, nact, tid, nthr);
+        init_slots(B, M, wg_slot0, nact, tid, nthr);
         __threadfence();
         __syncthreads();
         DStage S;
         S.B = &B; S.M = &M; S.lds = lds; S.cfg = &cfg; S.ci = wave; S.lane = lane; S.n = n; S.active = active; S.slot = slot; S.blk = blk;
-        S.src = active ? B.in + B.in_off[blk] : B.in;
-        S.nin = active ? (u32)(B.in_off[blk + 1] - B.in_off[blk]) : 0u;
-        S.dst = active ? B.out + B.out_off[blk] : B.out;
-        S.cap = active ? (u32)(B.out_off[blk + 1] - B.out_off[blk]) : 0u;
+        ZPG_BIND_IO(S, B, blk, active);
         S.prof[0] = S.prof[1] = S.prof[2] = S.prof[3] = 0;
         if (wave < n) {
-            switch (M.comp[wave].type) {                         // uniform per wave
-            case ZT_CONST: comp_dec<ZT_CONST>(S); break;
-            case ZT_CM: comp_dec<ZT_CM>(S); break;
-            case ZT_ICM: comp_dec<ZT_ICM>(S); break;
-            case ZT_MATCH: comp_dec<ZT_MATCH>(S); break;
-            case ZT_AVG: comp_dec<ZT_AVG>(S); break;
-            case ZT_MIX2: comp_dec<ZT_MIX2>(S); break;
-            case ZT_MIX: comp_dec<ZT_MIX>(S); break;
-            case ZT_ISSE: comp_dec<ZT_ISSE>(S); break;
-            default: comp_dec<ZT_SSE>(S); break;
-            }
+            ZPG_BY_TYPE(M.comp[wave].type, S, comp_dec, false, false);
         } else coder_dec(S);
 #ifdef ZPG_PROF
         if (blockIdx.x == 0 && lane == 0 && wave < n)
@@ -1461,17 +1409,7 @@ __global__ void __launch_bounds__(1024) k_wsetd(const DBatch B, const GCfg cfg)
     extern __shared__ __align__(16) u8 lds[];
     const DModel &M = *B.model;
     const int tid = threadIdx.x, nthr = blockDim.x;
-    {
-        u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
-        for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
-        u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
-        for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
-        for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
-        u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
-        for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
-        int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
-        for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
-    }
+    load_tables(B, lds, tid, nthr);
     __syncthreads();
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = cfg.n;
@@ -1481,23 +1419,10 @@ __global__ void __launch_bounds__(1024) k_wsetd(const DBatch B, const GCfg cfg)
     DStage S;
     S.B = &B; S.M = &M; S.lds = lds; S.cfg = &cfg; S.ci = wave; S.lane = lane; S.n = n; S.active = active; S.blk = blk;
     S.slot = B.slots + (u64)slot_ix * M.slot_bytes;              // (an inactive lane never dereferences it)
-    S.src = active ? B.in + B.in_off[blk] : B.in;
-    S.nin = active ? (u32)(B.in_off[blk + 1] - B.in_off[blk]) : 0u;
-    S.dst = active ? B.out + B.out_off[blk] : B.out;
-    S.cap = active ? (u32)(B.out_off[blk + 1] - B.out_off[blk]) : 0u;
+    ZPG_BIND_IO(S, B, blk, active);
     S.prof[0] = S.prof[1] = S.prof[2] = S.prof[3] = 0;
     if (wave < n) {
-        switch (M.comp[wave].type) {                             // uniform per wave
-        case ZT_CONST: comp_dec<ZT_CONST, false, true>(S); break;
-        case ZT_CM: comp_dec<ZT_CM, false, true>(S); break;
-        case ZT_ICM: comp_dec<ZT_ICM, false, true>(S); break;
-        case ZT_MATCH: comp_dec<ZT_MATCH, false, true>(S); break;
-        case ZT_AVG: comp_dec<ZT_AVG, false, true>(S); break;
-        case ZT_MIX2: comp_dec<ZT_MIX2, false, true>(S); break;
-        case ZT_MIX: comp_dec<ZT_MIX, false, true>(S); break;
-        case ZT_ISSE: comp_dec<ZT_ISSE, false, true>(S); break;
-        default: comp_dec<ZT_SSE, false, true>(S); break;
-        }
+        ZPG_BY_TYPE(M.comp[wave].type, S, comp_dec, false, true);
     } else coder_dec(S);
 }
 
@@ -1578,18 +1503,8 @@ __global__ void __launch_bounds__(1024) k_vpipe(const DBatch B, const VCfg V)
     const DModel &M = *B.model;
     const GCfg &cfg = V.g;
     const int tid = threadIdx.x, nthr = blockDim.x;
-    {
-        u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
-        for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
-        u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
-        for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
-        for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
-        u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
-        for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
-        int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
-        for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
-        for (int i = tid; i < M.hdr_len && i < ZPQ_MAX_HDR; i += nthr) lds[V.hdr_off + i] = M.header[i];
-    }
+    load_tables(B, lds, tid, nthr);
+    for (int i = tid; i < M.hdr_len && i < ZPQ_MAX_HDR; i += nthr) lds[V.hdr_off + i] = M.header[i];
     __syncthreads();
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = cfg.n;                                         // waves 0 .. n - 1: the components, n: the coder, n + 1: the interpreter
@@ -1608,7 +1523,7 @@ __global__ void __launch_bounds__(1024) k_vpipe(const DBatch B, const VCfg V)
         const int blk = base + lane;
         const bool active = lane_on && blk < B.nblocks;
         const int nact = min(wg_slots, B.nblocks - base);
-        init_slots(B, M, n, wg_slot0, nact, tid, nthr);          // (zeroes M, H and R with the rest of the slot: ZPAQL.clear)
+        init_slots(B, M, wg_slot0, nact, tid, nthr);          // (zeroes M, H and R with the rest of the slot: ZPAQL.clear)
         for (int i = tid; i < nctx; i += nthr) s_ctx[i] = 0u;    // byte 0 is coded under contexts of 0
         if (tid == 0) *misc = 0u;
         __threadfence();
@@ -1617,11 +1532,8 @@ __global__ void __launch_bounds__(1024) k_vpipe(const DBatch B, const VCfg V)
         Stage S;
         S.B = &B; S.M = &M; S.lds = lds; S.ci = wave; S.lane = lane; S.n = n; S.cfg = &cfg; S.active = active;
         S.slot = slot;
-        S.src = active ? B.in + B.in_off[blk] : B.in;
-        S.nin = active ? (u32)(B.in_off[blk + 1] - B.in_off[blk]) : 0u;
-        S.dst = active ? B.out + B.out_off[blk] : B.out;
-        S.cap = active ? (u32)(B.out_off[blk + 1] - B.out_off[blk]) : 0u;
-        S.total = active ? S.nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u) : 0u;
+        ZPG_BIND_IO(S, B, blk, active);
+        S.total = active ? S.nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u) : 0u;   // the bytes it codes, the PP byte included
         if (wave == 0) atomicMax(misc, S.total);
         __syncthreads();
         S.iters = *misc + (u32)n;
@@ -1631,25 +1543,11 @@ __global__ void __launch_bounds__(1024) k_vpipe(const DBatch B, const VCfg V)
         S.vmask = wave < n ? (u32)V.cmask[wave] : 0u;
         u32 opos = 0;
         if (wave < n) {
-            switch (M.comp[wave].type) {                         // uniform per wave
-            case ZT_CONST: comp_stage<ZT_CONST, BATCH, true>(S); break;
-            case ZT_CM: comp_stage<ZT_CM, BATCH, true>(S); break;
-            case ZT_ICM: comp_stage<ZT_ICM, BATCH, true>(S); break;
-            case ZT_MATCH: comp_stage<ZT_MATCH, BATCH, true>(S); break;
-            case ZT_AVG: comp_stage<ZT_AVG, BATCH, true>(S); break;
-            case ZT_MIX2: comp_stage<ZT_MIX2, BATCH, true>(S); break;
-            case ZT_MIX: comp_stage<ZT_MIX, BATCH, true>(S); break;
-            case ZT_ISSE: comp_stage<ZT_ISSE, BATCH, true>(S); break;
-            default: comp_stage<ZT_SSE, BATCH, true>(S); break;
-            }
+            ZPG_BY_TYPE(M.comp[wave].type, S, comp_stage, BATCH, true, false);
         } else if (wave == n) opos = coder_stage(S);
         else s_stat[lane] = vm_stage(S, V);
         __syncthreads();
-        if (wave == n && active) {
-            const i32 vst = s_stat[lane];
-            B.out_len[blk] = opos;
-            B.status[blk] = vst != ZPQ_OK ? vst : (opos > S.cap ? ZPQ_E_OVERFLOW : ZPQ_OK);
-        }
+        if (wave == n && active) put_result(B, blk, opos, S.cap, s_stat[lane]);
         __syncthreads();
     }
 }
@@ -1670,15 +1568,7 @@ __global__ void __launch_bounds__(1024) k_vset(const DBatch B, const VCfg V)
     u32 *const s_ctx = reinterpret_cast<u32 *>(lds + V.ctx_off);
     i32 *const s_stat = reinterpret_cast<i32 *>(lds + V.stat_off);
     {
-        u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
-        for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
-        u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
-        for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
-        for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
-        u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
-        for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
-        int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
-        for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
+        load_tables(B, lds, tid, nthr);
         for (int i = tid; i < M.hdr_len && i < ZPQ_MAX_HDR; i += nthr) lds[V.hdr_off + i] = M.header[i];
         const int nctx = (V.stat_off - V.ctx_off) / 4;
         for (int i = tid; i < nctx; i += nthr) s_ctx[i] = 0u;    // byte 0 of the segment is coded under contexts of 0
@@ -1694,11 +1584,8 @@ __global__ void __launch_bounds__(1024) k_vset(const DBatch B, const VCfg V)
     Stage S;
     S.B = &B; S.M = &M; S.lds = lds; S.ci = wave; S.lane = lane; S.n = n; S.cfg = &cfg; S.active = active;
     S.slot = B.slots + (u64)slot_ix * M.slot_bytes;              // (an inactive lane never dereferences it)
-    S.src = active ? B.in + B.in_off[blk] : B.in;
-    S.nin = active ? (u32)(B.in_off[blk + 1] - B.in_off[blk]) : 0u;
-    S.dst = active ? B.out + B.out_off[blk] : B.out;
-    S.cap = active ? (u32)(B.out_off[blk + 1] - B.out_off[blk]) : 0u;
-    S.total = active ? S.nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u) : 0u;
+    ZPG_BIND_IO(S, B, blk, active);
+    S.total = active ? S.nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u) : 0u;   // the bytes it codes, the PP byte included
     if (wave == 0) atomicMax(misc, S.total);
     __syncthreads();
     S.iters = *misc + (u32)n;
@@ -1708,25 +1595,11 @@ __global__ void __launch_bounds__(1024) k_vset(const DBatch B, const VCfg V)
     S.vmask = wave < n ? (u32)V.cmask[wave] : 0u;
     u32 opos = 0;
     if (wave < n) {
-        switch (M.comp[wave].type) {                             // uniform per wave
-        case ZT_CONST: comp_stage<ZT_CONST, BATCH, true, true>(S); break;
-        case ZT_CM: comp_stage<ZT_CM, BATCH, true, true>(S); break;
-        case ZT_ICM: comp_stage<ZT_ICM, BATCH, true, true>(S); break;
-        case ZT_MATCH: comp_stage<ZT_MATCH, BATCH, true, true>(S); break;
-        case ZT_AVG: comp_stage<ZT_AVG, BATCH, true, true>(S); break;
-        case ZT_MIX2: comp_stage<ZT_MIX2, BATCH, true, true>(S); break;
-        case ZT_MIX: comp_stage<ZT_MIX, BATCH, true, true>(S); break;
-        case ZT_ISSE: comp_stage<ZT_ISSE, BATCH, true, true>(S); break;
-        default: comp_stage<ZT_SSE, BATCH, true, true>(S); break;
-        }
+        ZPG_BY_TYPE(M.comp[wave].type, S, comp_stage, BATCH, true, true);
     } else if (wave == n) opos = coder_stage(S);
     else s_stat[lane] = vm_stage<true>(S, V);
     __syncthreads();
-    if (wave == n && active) {
-        const i32 vst = s_stat[lane];
-        B.out_len[blk] = opos;
-        B.status[blk] = vst != ZPQ_OK ? vst : (opos > S.cap ? ZPQ_E_OVERFLOW : ZPQ_OK);
-    }
+    if (wave == n && active) put_result(B, blk, opos, S.cap, s_stat[lane]);
 }
 
 // The interpreter wave of the decoder: it keeps step with the bits (the same barriers as every wave), collects the byte
@@ -1787,18 +1660,8 @@ __global__ void __launch_bounds__(1024) k_vdec(const DBatch B, const VCfg V)
     const DModel &M = *B.model;
     const GCfg &cfg = V.g;
     const int tid = threadIdx.x, nthr = blockDim.x;
-    {
-        u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
-        for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
-        u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
-        for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
-        for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
-        u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
-        for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
-        int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
-        for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
-        for (int i = tid; i < M.hdr_len && i < ZPQ_MAX_HDR; i += nthr) lds[V.hdr_off + i] = M.header[i];
-    }
+    load_tables(B, lds, tid, nthr);
+    for (int i = tid; i < M.hdr_len && i < ZPQ_MAX_HDR; i += nthr) lds[V.hdr_off + i] = M.header[i];
     __syncthreads();
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = cfg.n;                                         // waves 0 .. n - 1: the components, n: the decoder, n + 1: the interpreter
@@ -1815,30 +1678,17 @@ __global__ void __launch_bounds__(1024) k_vdec(const DBatch B, const VCfg V)
         const int blk = base + lane;
         const bool active = lane_on && blk < B.nblocks;
         const int nact = min(wg_slots, B.nblocks - base);
-        init_slots(B, M, n, wg_slot0, nact, tid, nthr);
+        init_slots(B, M, wg_slot0, nact, tid, nthr);
         for (int i = tid; i < n * BPW; i += nthr) s_h[i] = 0u;   // the first byte is decoded under contexts of 0
         __threadfence();
         __syncthreads();
         DStage S;
         S.B = &B; S.M = &M; S.lds = lds; S.cfg = &cfg; S.ci = wave; S.lane = lane; S.n = n; S.active = active; S.slot = slot; S.blk = blk;
-        S.src = active ? B.in + B.in_off[blk] : B.in;
-        S.nin = active ? (u32)(B.in_off[blk + 1] - B.in_off[blk]) : 0u;
-        S.dst = active ? B.out + B.out_off[blk] : B.out;
-        S.cap = active ? (u32)(B.out_off[blk + 1] - B.out_off[blk]) : 0u;
+        ZPG_BIND_IO(S, B, blk, active);
         S.prof[0] = S.prof[1] = S.prof[2] = S.prof[3] = 0;
         S.vctx = s_h + (wave < n ? wave : 0) * BPW + lane;
         if (wave < n) {
-            switch (M.comp[wave].type) {                         // uniform per wave
-            case ZT_CONST: comp_dec<ZT_CONST, true>(S); break;
-            case ZT_CM: comp_dec<ZT_CM, true>(S); break;
-            case ZT_ICM: comp_dec<ZT_ICM, true>(S); break;
-            case ZT_MATCH: comp_dec<ZT_MATCH, true>(S); break;
-            case ZT_AVG: comp_dec<ZT_AVG, true>(S); break;
-            case ZT_MIX2: comp_dec<ZT_MIX2, true>(S); break;
-            case ZT_MIX: comp_dec<ZT_MIX, true>(S); break;
-            case ZT_ISSE: comp_dec<ZT_ISSE, true>(S); break;
-            default: comp_dec<ZT_SSE, true>(S); break;
-            }
+            ZPG_BY_TYPE(M.comp[wave].type, S, comp_dec, true, false);
         } else if (wave == n) coder_dec(S);
         else s_stat[lane] = vm_dec(S, V);
         __syncthreads();
@@ -1858,15 +1708,7 @@ __global__ void __launch_bounds__(1024) k_vsetd(const DBatch B, const VCfg V)
     i32 *const s_stat = reinterpret_cast<i32 *>(lds + V.stat_off);
     const int n = cfg.n;                                         // waves 0 .. n - 1: the components, n: the decoder, n + 1: the interpreter
     {
-        u32 *st = reinterpret_cast<u32 *>(lds + L_STRETCH);
-        for (int i = tid; i < 2048 + 128; i += nthr) st[i] = B.stretch_c[i];
-        u16 *sq = reinterpret_cast<u16 *>(lds + L_SQUASH);
-        for (int i = tid; i < 4096; i += nthr) sq[i] = (u16)B.squash[i];
-        for (int i = tid; i < 1024; i += nthr) lds[L_NS + i] = B.ns[i];
-        u32 *dt = reinterpret_cast<u32 *>(lds + L_DT);
-        for (int i = tid; i < 1024; i += nthr) dt[i] = B.dt[i];
-        int16_t *d2 = reinterpret_cast<int16_t *>(lds + L_DT2K);
-        for (int i = tid; i < 256; i += nthr) d2[i] = B.dt2k[i];
+        load_tables(B, lds, tid, nthr);
         for (int i = tid; i < M.hdr_len && i < ZPQ_MAX_HDR; i += nthr) lds[V.hdr_off + i] = M.header[i];
         for (int i = tid; i < n * BPW; i += nthr) s_h[i] = 0u;   // the segment's first byte is decoded under contexts of 0
     }
@@ -1878,24 +1720,11 @@ __global__ void __launch_bounds__(1024) k_vsetd(const DBatch B, const VCfg V)
     DStage S;
     S.B = &B; S.M = &M; S.lds = lds; S.cfg = &cfg; S.ci = wave; S.lane = lane; S.n = n; S.active = active; S.blk = blk;
     S.slot = B.slots + (u64)slot_ix * M.slot_bytes;              // (an inactive lane never dereferences it)
-    S.src = active ? B.in + B.in_off[blk] : B.in;
-    S.nin = active ? (u32)(B.in_off[blk + 1] - B.in_off[blk]) : 0u;
-    S.dst = active ? B.out + B.out_off[blk] : B.out;
-    S.cap = active ? (u32)(B.out_off[blk + 1] - B.out_off[blk]) : 0u;
+    ZPG_BIND_IO(S, B, blk, active);
     S.prof[0] = S.prof[1] = S.prof[2] = S.prof[3] = 0;
     S.vctx = s_h + (wave < n ? wave : 0) * BPW + lane;
     if (wave < n) {
-        switch (M.comp[wave].type) {                             // uniform per wave
-        case ZT_CONST: comp_dec<ZT_CONST, true, true>(S); break;
-        case ZT_CM: comp_dec<ZT_CM, true, true>(S); break;
-        case ZT_ICM: comp_dec<ZT_ICM, true, true>(S); break;
-        case ZT_MATCH: comp_dec<ZT_MATCH, true, true>(S); break;
-        case ZT_AVG: comp_dec<ZT_AVG, true, true>(S); break;
-        case ZT_MIX2: comp_dec<ZT_MIX2, true, true>(S); break;
-        case ZT_MIX: comp_dec<ZT_MIX, true, true>(S); break;
-        case ZT_ISSE: comp_dec<ZT_ISSE, true, true>(S); break;
-        default: comp_dec<ZT_SSE, true, true>(S); break;
-        }
+        ZPG_BY_TYPE(M.comp[wave].type, S, comp_dec, true, true);
     } else if (wave == n) coder_dec(S);
     else s_stat[lane] = vm_dec<true>(S, V);
     __syncthreads();
@@ -2036,6 +1865,32 @@ static int occupancy_wgs(const void *fn, int threads, size_t lds, int bound)
     return nb < bound ? nb : bound;
 }
 
+// One launch of a kernel of this file: the workgroup may take all of a CU's LDS.
+template <class K, class C>
+static void launch_waves(K kernel, dim3 grid, dim3 threads, size_t lds, hipStream_t stream, const DBatch *B, const C &cfg)
+{
+    (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL(kernel, grid, threads, lds, stream, *B, cfg);
+}
+// An encoder: its byte-batched instantiation, or with ZPQ_GPIPE_BATCH=0 the bit-serial one (tests compare the two).
+template <class K, class C>
+static void launch_encoder(K batched, K bit_serial, dim3 grid, dim3 threads, size_t lds, hipStream_t stream, const DBatch *B, const C &cfg)
+{
+    const char *ev = getenv("ZPQ_GPIPE_BATCH");
+    launch_waves(ev && atoi(ev) == 0 ? bit_serial : batched, grid, threads, lds, stream, B, cfg);
+}
+// Lanes in use per workgroup of k_gdec / k_vdec: 64.  (Spreading a batch that leaves workgroup slots empty over more
+// workgroups of 32 or 16 lanes was measured: C4b, 16 384 blocks: 2368 ms at 64 lanes, 3056 at 32, 4927 at 16 -- a bit costs
+// a wave the same whatever its lanes; ZPQ_GDEC_BPW keeps the knob.)
+static int gdec_bpw()
+{
+    const char *ev = getenv("ZPQ_GDEC_BPW");
+    const int v = ev ? atoi(ev) : 0;
+    return v == 16 || v == 32 ? v : zpqg::BPW;
+}
+// A block set's call: entry i on slot B->slot_map[i] (no identity map: the slots are the set's), every entry a member.
+static bool set_call_ok(const DBatch *B) { return B->nblocks >= 1 && B->nslots == B->nblocks && B->slot_map; }
+
 extern "C" int zpq_gpipe_blocks_per_cu(const DModel *M)
 {
     zpqg::GCfg cfg;
@@ -2056,14 +1911,7 @@ extern "C" int zpq_launch_gpipe(const DBatch *B, const DModel *hostM, int nslots
     size_t lds = 0;
     if (!gpipe_cfg(hostM, &cfg, &lds)) return ZPQ_E_INTERNAL;
     const int nwg = (nslots + zpqg::BPW - 1) / zpqg::BPW;
-    const char *ev = getenv("ZPQ_GPIPE_BATCH");                   // "0": the bit-serial stages (tests compare the two)
-    if (ev && atoi(ev) == 0) {
-        (void)hipFuncSetAttribute((const void *)zpqg::k_gpipe<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(zpqg::k_gpipe<false>, dim3(nwg), dim3(64 * (cfg.n + 1)), lds, stream, *B, cfg);
-    } else {
-        (void)hipFuncSetAttribute((const void *)zpqg::k_gpipe<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(zpqg::k_gpipe<true>, dim3(nwg), dim3(64 * (cfg.n + 1)), lds, stream, *B, cfg);
-    }
+    launch_encoder(zpqg::k_gpipe<true>, zpqg::k_gpipe<false>, dim3(nwg), dim3(64 * (cfg.n + 1)), lds, stream, B, cfg);
     return ZPQ_OK;
 }
 
@@ -2104,16 +1952,9 @@ extern "C" int zpq_launch_gdec(const DBatch *B, const DModel *hostM, int nslots,
     zpqg::GCfg cfg;
     size_t lds = 0, dlds = 0;
     if (!gpipe_cfg(hostM, &cfg, &lds, &dlds)) return ZPQ_E_INTERNAL;
-    // 64 blocks per workgroup.  (Spreading a batch that leaves workgroup slots empty over more workgroups of 32 or 16 lanes
-    // was measured: C4b, 16 384 blocks: 2368 ms at 64 lanes, 3056 at 32, 4927 at 16 -- a bit costs a wave the same whatever
-    // its lanes; ZPQ_GDEC_BPW keeps the knob.)
-    const char *ev = getenv("ZPQ_GDEC_BPW");
-    int bpw = zpqg::BPW;
-    if (ev && (atoi(ev) == 16 || atoi(ev) == 32 || atoi(ev) == 64)) bpw = atoi(ev);
-    cfg.bpw = bpw;
-    const int nwg = (nslots + bpw - 1) / bpw;
-    (void)hipFuncSetAttribute((const void *)zpqg::k_gdec, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(zpqg::k_gdec, dim3(nwg), dim3(64 * (cfg.n + 1)), dlds, stream, *B, cfg);
+    cfg.bpw = gdec_bpw();
+    const int nwg = (nslots + cfg.bpw - 1) / cfg.bpw;
+    launch_waves(zpqg::k_gdec, dim3(nwg), dim3(64 * (cfg.n + 1)), dlds, stream, B, cfg);
     return ZPQ_OK;
 }
 
@@ -2125,25 +1966,12 @@ extern "C" int zpq_launch_wset(const DBatch *B, const DModel *hostM, int decode,
 {
     zpqg::GCfg cfg;
     size_t lds = 0, dlds = 0;
-    if (!gpipe_cfg(hostM, &cfg, &lds, &dlds) || dlds > 160 * 1024) return ZPQ_E_INTERNAL;
-    if (B->nblocks < 1 || B->nslots != B->nblocks || !B->slot_map) return ZPQ_E_INTERNAL;   // (no identity map: the slots are the set's)
+    if (!gpipe_cfg(hostM, &cfg, &lds, &dlds) || dlds > 160 * 1024 || !set_call_ok(B)) return ZPQ_E_INTERNAL;
     cfg.bpw = zpqg::BPW;
     const dim3 g((B->nblocks + zpqg::BPW - 1) / zpqg::BPW), t(64 * (cfg.n + 1));
-    if (decode) {
-        (void)hipFuncSetAttribute((const void *)zpqg::k_wsetd, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(zpqg::k_wsetd, g, t, dlds, stream, *B, cfg);
-        *name = "k_wsetd<decode>";
-        return ZPQ_OK;
-    }
-    const char *ev = getenv("ZPQ_GPIPE_BATCH");
-    if (ev && atoi(ev) == 0) {
-        (void)hipFuncSetAttribute((const void *)zpqg::k_wset<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(zpqg::k_wset<false>, g, t, lds, stream, *B, cfg);
-    } else {
-        (void)hipFuncSetAttribute((const void *)zpqg::k_wset<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(zpqg::k_wset<true>, g, t, lds, stream, *B, cfg);
-    }
-    *name = "k_wset<encode>";
+    if (decode) launch_waves(zpqg::k_wsetd, g, t, dlds, stream, B, cfg);
+    else launch_encoder(zpqg::k_wset<true>, zpqg::k_wset<false>, g, t, lds, stream, B, cfg);
+    *name = decode ? "k_wsetd<decode>" : "k_wset<encode>";
     return ZPQ_OK;
 }
 
@@ -2207,14 +2035,7 @@ extern "C" int zpq_launch_vpipe(const DBatch *B, const DModel *hostM, int nslots
     if (!vpipe_cfg(hostM, &V, &lds, &dlds)) return ZPQ_E_INTERNAL;
     vpipe_offsets(&V, lds, (int)(V.coff[V.g.n - 1] + V.cmask[V.g.n - 1] + 1) * zpqg::BPW, hostM->hdr_len);
     const int nwg = (nslots + zpqg::BPW - 1) / zpqg::BPW;
-    const char *ev = getenv("ZPQ_GPIPE_BATCH");                   // "0": the bit-serial stages, as for k_gpipe
-    if (ev && atoi(ev) == 0) {
-        (void)hipFuncSetAttribute((const void *)zpqg::k_vpipe<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(zpqg::k_vpipe<false>, dim3(nwg), dim3(64 * (V.g.n + 2)), lds, stream, *B, V);
-    } else {
-        (void)hipFuncSetAttribute((const void *)zpqg::k_vpipe<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(zpqg::k_vpipe<true>, dim3(nwg), dim3(64 * (V.g.n + 2)), lds, stream, *B, V);
-    }
+    launch_encoder(zpqg::k_vpipe<true>, zpqg::k_vpipe<false>, dim3(nwg), dim3(64 * (V.g.n + 2)), lds, stream, B, V);
     return ZPQ_OK;
 }
 
@@ -2224,13 +2045,9 @@ extern "C" int zpq_launch_vdec(const DBatch *B, const DModel *hostM, int nslots,
     size_t lds = 0, dlds = 0;
     if (!vpipe_cfg(hostM, &V, &lds, &dlds)) return ZPQ_E_INTERNAL;
     vpipe_offsets(&V, dlds, V.g.n * zpqg::BPW, hostM->hdr_len);
-    const char *ev = getenv("ZPQ_GDEC_BPW");                      // as for k_gdec
-    int bpw = zpqg::BPW;
-    if (ev && (atoi(ev) == 16 || atoi(ev) == 32 || atoi(ev) == 64)) bpw = atoi(ev);
-    V.g.bpw = bpw;
-    const int nwg = (nslots + bpw - 1) / bpw;
-    (void)hipFuncSetAttribute((const void *)zpqg::k_vdec, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(zpqg::k_vdec, dim3(nwg), dim3(64 * (V.g.n + 2)), dlds, stream, *B, V);
+    V.g.bpw = gdec_bpw();
+    const int nwg = (nslots + V.g.bpw - 1) / V.g.bpw;
+    launch_waves(zpqg::k_vdec, dim3(nwg), dim3(64 * (V.g.n + 2)), dlds, stream, B, V);
     return ZPQ_OK;
 }
 
@@ -2242,26 +2059,16 @@ extern "C" int zpq_launch_vset(const DBatch *B, const DModel *hostM, int decode,
 {
     zpqg::VCfg V;
     size_t lds = 0, dlds = 0;
-    if (!vpipe_cfg(hostM, &V, &lds, &dlds)) return ZPQ_E_INTERNAL;
-    if (B->nblocks < 1 || B->nslots != B->nblocks || !B->slot_map) return ZPQ_E_INTERNAL;   // (no identity map: the slots are the set's)
+    if (!vpipe_cfg(hostM, &V, &lds, &dlds) || !set_call_ok(B)) return ZPQ_E_INTERNAL;
     V.g.bpw = zpqg::BPW;
     const dim3 g((B->nblocks + zpqg::BPW - 1) / zpqg::BPW), t(64 * (V.g.n + 2));
     if (decode) {
         vpipe_offsets(&V, dlds, V.g.n * zpqg::BPW, hostM->hdr_len);
-        (void)hipFuncSetAttribute((const void *)zpqg::k_vsetd, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(zpqg::k_vsetd, g, t, dlds, stream, *B, V);
-        *name = "k_vsetd<decode>";
-        return ZPQ_OK;
-    }
-    vpipe_offsets(&V, lds, (int)(V.coff[V.g.n - 1] + V.cmask[V.g.n - 1] + 1) * zpqg::BPW, hostM->hdr_len);
-    const char *ev = getenv("ZPQ_GPIPE_BATCH");
-    if (ev && atoi(ev) == 0) {
-        (void)hipFuncSetAttribute((const void *)zpqg::k_vset<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(zpqg::k_vset<false>, g, t, lds, stream, *B, V);
+        launch_waves(zpqg::k_vsetd, g, t, dlds, stream, B, V);
     } else {
-        (void)hipFuncSetAttribute((const void *)zpqg::k_vset<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(zpqg::k_vset<true>, g, t, lds, stream, *B, V);
+        vpipe_offsets(&V, lds, (int)(V.coff[V.g.n - 1] + V.cmask[V.g.n - 1] + 1) * zpqg::BPW, hostM->hdr_len);
+        launch_encoder(zpqg::k_vset<true>, zpqg::k_vset<false>, g, t, lds, stream, B, V);
     }
-    *name = "k_vset<encode>";
+    *name = decode ? "k_vsetd<decode>" : "k_vset<encode>";
     return ZPQ_OK;
 }

@@ -34,6 +34,7 @@
 #include "zpq_common.h"
 #include "zpq_vm.h"
 #include "zpq_host.h"
+#include "zpq_dev.h"
 
 namespace zpql {
 
@@ -45,6 +46,7 @@ typedef uint16_t u16;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 using zpqvm::Vm;
 using zpqvm::vm_run;
+using namespace zpqdev;
 
 constexpr int WAVES = 4;                         // blocks per workgroup
 constexpr int L_STRETCH = 0;                     // u32[2048+128]
@@ -79,9 +81,6 @@ struct LCfg {
 #define LPROF(k) do { } while (0)
 #endif
 
-__device__ __forceinline__ i32 wadd(i32 a, i32 b) { return (i32)((u32)a + (u32)b); }
-__device__ __forceinline__ i32 wsub(i32 a, i32 b) { return (i32)((u32)a - (u32)b); }
-__device__ __forceinline__ i32 wmul(i32 a, i32 b) { return (i32)((u32)a * (u32)b); }
 // sum over the 64 lanes: four DPP row shifts leave each row's total in its lane 15, then four v_readlane
 __device__ __forceinline__ i32 wave_sum(i32 x)
 {
@@ -92,8 +91,6 @@ __device__ __forceinline__ i32 wave_sum(i32 x)
     return wadd(wadd(__builtin_amdgcn_readlane(x, 15), __builtin_amdgcn_readlane(x, 31)),
                 wadd(__builtin_amdgcn_readlane(x, 47), __builtin_amdgcn_readlane(x, 63)));
 }
-__device__ __forceinline__ i32 clamp2k(i32 x) { return min(max(x, -2048), 2047); }
-__device__ __forceinline__ i32 clamp512k(i32 x) { return min(max(x, -262144), 262143); }
 
 // VMH: the program is the shipped hash chain (cfg.vm_hashes > 0), evaluated in registers -- such launches do not carry
 // the ZPAQL interpreter at all (fewer registers, no spills); any other program runs through it on lane 0.
@@ -180,24 +177,10 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
         // ---- Predictor.init + ZPAQL.clear (predictor.v:325-470, zpaql.v:54-95): the wave zeroes
         //      its slot with 16-B stores, then fills the non-zero tables
         if (!KEEP) {
-            uint4 *z4 = reinterpret_cast<uint4 *>(slot);
-            const u64 n16 = M.zero_bytes / 16;
-            const uint4 zero = make_uint4(0, 0, 0, 0);
-            for (u64 i = lane; i < n16; i += 64) z4[i] = zero;
+            slot_zero(M, slot, lane, 64);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();
-            for (i32 ci = 0; ci < n; ci++) {
-                const DComp &c = M.comp[ci];
-                if (c.cm_len && c.cm_fill != ZF_ZERO) {
-                    u32 *t = reinterpret_cast<u32 *>(slot + c.cm_off);
-                    if (c.cm_fill == ZF_CONST) { for (u32 i = lane; i < c.cm_len; i += 64) t[i] = c.cm_fill_val; }
-                    else { const u32 *img = B.img + c.cm_fill_val; for (u32 i = lane; i < c.cm_len; i += 64) t[i] = img[i % c.cm_pat_len]; }
-                }
-                if (c.a16_len && c.a16_fill) {
-                    u16 *t = reinterpret_cast<u16 *>(slot + c.a16_off);
-                    for (u32 i = lane; i < c.a16_len; i += 64) t[i] = (u16)c.a16_fill;
-                }
-            }
+            slot_fill(M, B.img, slot, lane, 64);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -719,24 +702,10 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
 
     for (int blk = slot_id; slot_id < nslots && blk < B.nblocks; blk += nslots) {
         if (!KEEP) {   // Predictor.init + ZPAQL.clear: the row zeroes its slot, then fills the non-zero tables
-            uint4 *z4 = reinterpret_cast<uint4 *>(slot);
-            const u64 n16 = M.zero_bytes / 16;
-            const uint4 zero = make_uint4(0, 0, 0, 0);
-            for (u64 i = li; i < n16; i += RL) z4[i] = zero;
+            slot_zero(M, slot, li, RL);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();
-            for (i32 ci = 0; ci < n; ci++) {
-                const DComp &c = M.comp[ci];
-                if (c.cm_len && c.cm_fill != ZF_ZERO) {
-                    u32 *t = reinterpret_cast<u32 *>(slot + c.cm_off);
-                    if (c.cm_fill == ZF_CONST) { for (u32 i = li; i < c.cm_len; i += RL) t[i] = c.cm_fill_val; }
-                    else { const u32 *img = B.img + c.cm_fill_val; for (u32 i = li; i < c.cm_len; i += RL) t[i] = img[i % c.cm_pat_len]; }
-                }
-                if (c.a16_len && c.a16_fill) {
-                    u16 *t = reinterpret_cast<u16 *>(slot + c.a16_off);
-                    for (u32 i = li; i < c.a16_len; i += RL) t[i] = (u16)c.a16_fill;
-                }
-            }
+            slot_fill(M, B.img, slot, li, RL);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -1129,33 +1098,16 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
 
 // Predictor.init + ZPAQL.clear (predictor.v:325-470, zpaql.v:54-95) of every member of a block set in one launch, in the
 // form the KEEP kernels load: the slot zeroed, the ZF_CONST / ZF_PATTERN tables and the a16 tables filled, MATCH's
-// initial scalars (quirk Q17: sizebits / bufbits left in a / b).  One workgroup per slot.
+// initial scalars (quirk Q17: sizebits / bufbits left in a / b).  One workgroup per slot.  Sets of chain models start here
+// too (k_chain<..., KEEP> loads the same form; such a model has no ZF_CONST table and no MATCH).
 __global__ void __launch_bounds__(256) k_set_init(const DModel *Mp, const uint32_t *img, uint8_t *slots)
 {
     const DModel &M = *Mp;
     u8 *slot = slots + (u64)blockIdx.x * M.slot_bytes;
-    uint4 *z4 = reinterpret_cast<uint4 *>(slot);
-    const u64 n16 = M.zero_bytes / 16;
-    const uint4 zero = make_uint4(0, 0, 0, 0);
-    for (u64 i = threadIdx.x; i < n16; i += 256) z4[i] = zero;
+    slot_zero(M, slot, threadIdx.x, 256);
     __syncthreads();                                              // (a workgroup's own stores, in order, before the fills)
-    for (i32 ci = 0; ci < M.n; ci++) {
-        const DComp &c = M.comp[ci];
-        if (c.cm_len && c.cm_fill != ZF_ZERO) {
-            u32 *t = reinterpret_cast<u32 *>(slot + c.cm_off);
-            if (c.cm_fill == ZF_CONST) { for (u32 i = threadIdx.x; i < c.cm_len; i += 256) t[i] = c.cm_fill_val; }
-            else { const u32 *im = img + c.cm_fill_val; for (u32 i = threadIdx.x; i < c.cm_len; i += 256) t[i] = im[i % c.cm_pat_len]; }
-        }
-        if (c.a16_len && c.a16_fill) {
-            u16 *t = reinterpret_cast<u16 *>(slot + c.a16_off);
-            for (u32 i = threadIdx.x; i < c.a16_len; i += 256) t[i] = (u16)c.a16_fill;
-        }
-        if (c.type == ZT_MATCH && threadIdx.x == 0) {
-            DCompScal *gs = reinterpret_cast<DCompScal *>(slot + M.scal_off);
-            gs[ci].a = c.a;
-            gs[ci].b = c.b;
-        }
-    }
+    slot_fill(M, img, slot, threadIdx.x, 256);
+    slot_match_init(M, slot, threadIdx.x, 256);
 }
 
 }  // namespace zpql
@@ -1214,7 +1166,7 @@ extern "C" const char *zpq_lanes_kernel_name(const DModel *M, int decode)
     return rows ? (decode ? "k_rows<decode>" : "k_rows<encode>") : (decode ? "k_lanes<decode>" : "k_lanes<encode>");
 }
 
-// block sets: Predictor.init + ZPAQL.clear of nmembers slots (the KEEP launches below never initialise)
+// block sets: Predictor.init + ZPAQL.clear of nmembers slots (no KEEP launch of any kernel family initialises)
 extern "C" int zpq_launch_lanes_set_init(const DModel *d_model, const uint32_t *d_img, uint8_t *slots, int nmembers, hipStream_t stream)
 {
     if (nmembers < 1) return ZPQ_E_INTERNAL;

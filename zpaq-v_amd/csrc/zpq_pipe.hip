@@ -27,21 +27,12 @@
 #include "../../include/zpaq_hip.h"
 #include "zpq_common.h"
 #include "zpq_chain_cfg.h"
+#include "zpq_dev.h"
 
 namespace zpqp {
 
 using namespace zpqc;
-
-__device__ __forceinline__ i32 wadd(i32 a, i32 b) { return (i32)((u32)a + (u32)b); }
-__device__ __forceinline__ i32 wmul(i32 a, i32 b) { return (i32)((u32)a * (u32)b); }
-__device__ __forceinline__ i32 clamp2k(i32 x) { return min(max(x, -2048), 2047); }
-__device__ __forceinline__ i32 clamp512k(i32 x) { return min(max(x, -262144), 262143); }
-__device__ __forceinline__ uint32_t mul_shr16(uint32_t range, uint32_t p16)   // see zpq_chain.hip
-{
-    return (uint32_t)__umul24(range >> 16, p16) + ((uint32_t)__umul24(range & 0xFFFFu, p16) >> 16);
-}
-// LDS traffic of this wave done, then the workgroup barrier (no wait for global memory: the row prefetch stays in flight)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+using namespace zpqdev;
 
 // Striped upload (host_pipeline, DBatch::gate_flag): the rest of the input may still be crossing PCIe.  Wait for the
 // host's signal (an acquire at system scope, so that nothing read afterwards is stale); bounded, so that a host that
