@@ -140,6 +140,12 @@ const char *zpq_ctx_last_kernel_name(const zpq_ctx *);
  * out[out_off[b] ...], at most out_off[b+1]-out_off[b] of them; out_len[b] =
  * byte count.  status[b] = ZPQ_OK / ZPQ_E_OVERFLOW / ZPQ_E_VMSTEPS.
  * Host-pointer form: copies in/out over PCIe around the kernel.
+ * The window contract: in_off[] / out_off[] are windows into the caller's buffers.
+ * For any nblocks >= 1 the host-pointer forms (these two, their _multi forms,
+ * zpq_sha1_blocks, zpq_blockset_*_segments) read only in[in_off[0] .. in_off[nblocks])
+ * and write only inside out[out_off[0] .. out_off[nblocks]).  Neither first offset
+ * need be 0, and an offset beyond 2^32 is an offset like any other: the one bound is
+ * on a single slab, out_off[b+1] - out_off[b] <= 4 GiB - 16 (and the same for in_off).
  */
 int zpq_encode_blocks(zpq_ctx *, const zpq_model *, int nblocks, const uint8_t *in,
                       const uint64_t *in_off, uint32_t flags, uint8_t *out,
@@ -203,9 +209,10 @@ int zpq_decode_blocks_multi(zpq_ctx *const *ctxs, int nctx, const zpq_model *, i
  * synchronize, or an event the ctx stream waits on) before calling, and must zpq_ctx_sync()
  * (or wait on zpq_ctx_stream()) before consuming the results on another stream.
  * Threading contract: the host-pointer entry points (zpq_encode_blocks, zpq_decode_blocks,
- * zpq_sha1_blocks, zpq_block_*) serialise on a per-ctx mutex and may be called from several
- * threads; the _dev forms take no lock -- one thread per ctx at a time (they share the ctx's
- * slot pool and stream), which is how the one-thread-per-device design of SURVEY 8(e) uses them. */
+ * zpq_sha1_blocks, zpq_block_*, zpq_blockset_*, and zpq_*_blocks_multi on each ctx it is
+ * given) serialise on a per-ctx mutex and may be called from several threads; the _dev
+ * forms take no lock -- one thread per ctx at a time (they share the ctx's slot pool and
+ * stream), which is how the one-thread-per-device design of SURVEY 8(e) uses them. */
 int zpq_encode_blocks_dev(zpq_ctx *, const zpq_model *, int nblocks, const uint8_t *in,
                           const uint64_t *in_off, uint32_t flags, uint8_t *out,
                           const uint64_t *out_off, uint32_t *out_len, int32_t *status);

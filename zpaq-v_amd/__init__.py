@@ -7,6 +7,6 @@ registers it as module ``zpaq_v_amd``.
 """
 from .binding import (  # noqa: F401
     FLAG_GENERIC, FLAG_LANES, FLAG_PP, FLAG_VMPIPE, SET_LANES, SET_PIPE, SET_VMWAVES, SET_WAVES, Block, BlockSet, Context, Model, PinnedArray, ZpqError, level_header, lib, lib_path,
-    scan_header, status_string,
+    decode_blocks_multi, encode_blocks_multi, scan_header, status_string,
 )
 from .frontend import Compressor, Decompresser, archive_add, archive_extract  # noqa: F401,E402

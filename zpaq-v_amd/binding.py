@@ -243,6 +243,42 @@ def _offsets(lengths):
     return off
 
 
+# fn(*head, in, in_off, flags, out, out_off, results...): the batch, _multi and block-set calls differ in `head` alone
+def _enc_raw(fn, head, nblocks, in_ptr, in_off, flags, out_ptr, out_off):
+    in_off, out_off = np.ascontiguousarray(in_off, dtype=np.uint64), np.ascontiguousarray(out_off, dtype=np.uint64)
+    assert len(in_off) == nblocks + 1 and len(out_off) == nblocks + 1
+    out_len = np.full(nblocks, 0xABCDEF, dtype=np.uint32)
+    status = np.full(nblocks, -99, dtype=np.int32)
+    rc = fn(*head, in_ptr, in_off.ctypes.data, flags, out_ptr, out_off.ctypes.data, out_len.ctypes.data,
+            status.ctypes.data)
+    return rc, out_len, status
+
+
+def _dec_raw(fn, head, nblocks, in_ptr, in_off, flags, out_ptr, out_off):
+    in_off, out_off = np.ascontiguousarray(in_off, dtype=np.uint64), np.ascontiguousarray(out_off, dtype=np.uint64)
+    assert len(in_off) == nblocks + 1 and len(out_off) == nblocks + 1
+    r = [np.full(nblocks, 0xABCDEF, dtype=np.uint32) for _ in range(4)]
+    status = np.full(nblocks, -99, dtype=np.int32)
+    rc = fn(*head, in_ptr, in_off.ctypes.data, flags, out_ptr, out_off.ctypes.data, r[0].ctypes.data,
+            r[1].ctypes.data, r[2].ctypes.data, r[3].ctypes.data, status.ctypes.data)
+    return rc, r[0], r[1], r[2], r[3], status
+
+
+def _ctx_array(ctxs):
+    return (C.c_void_p * len(ctxs))(*[c.h for c in ctxs]), len(ctxs)
+
+
+def encode_blocks_multi(ctxs, model, nblocks, in_ptr, in_off, flags, out_ptr, out_off):
+    """zpq_encode_blocks_multi over the Contexts `ctxs` (one may be listed several times) on caller buffers.
+    Returns (rc, out_len, status)."""
+    return _enc_raw(lib().zpq_encode_blocks_multi, _ctx_array(ctxs) + (model.h, nblocks), nblocks, in_ptr, in_off, flags, out_ptr, out_off)
+
+
+def decode_blocks_multi(ctxs, model, nblocks, in_ptr, in_off, flags, out_ptr, out_off):
+    """zpq_decode_blocks_multi likewise.  Returns (rc, out_len, consumed, final_code, first_byte, status)."""
+    return _dec_raw(lib().zpq_decode_blocks_multi, _ctx_array(ctxs) + (model.h, nblocks), nblocks, in_ptr, in_off, flags, out_ptr, out_off)
+
+
 class Context:
     """One GPU (zpq_ctx).  Batch helpers take/return Python bytes for tests; the
     *_dev forms take raw device pointers (e.g. torch tensors' data_ptr())."""
@@ -373,6 +409,29 @@ class Context:
         _ck(lib().zpq_decode_blocks_dev(self.h, model.h, nblocks, d_in, d_in_off, flags, d_out, d_out_off,
                                         d_out_len, d_consumed, d_code, d_first, d_status),
             "zpq_decode_blocks_dev")
+
+    # ---- raw forms: the caller's own buffers and offsets (any window of them), nothing raised -- rc comes back first
+    def encode_blocks_raw(self, model, nblocks, in_ptr, in_off, flags, out_ptr, out_off):
+        """zpq_encode_blocks on caller buffers: in_ptr / out_ptr are host addresses, in_off / out_off uint64 arrays of
+        nblocks + 1 entries (in_off[0] and out_off[0] need not be 0).  Returns (rc, out_len, status)."""
+        return _enc_raw(lib().zpq_encode_blocks, (self.h, model.h, nblocks), nblocks, in_ptr, in_off, flags, out_ptr, out_off)
+
+    def decode_blocks_raw(self, model, nblocks, in_ptr, in_off, flags, out_ptr, out_off):
+        """zpq_decode_blocks likewise.  Returns (rc, out_len, consumed, final_code, first_byte, status)."""
+        return _dec_raw(lib().zpq_decode_blocks, (self.h, model.h, nblocks), nblocks, in_ptr, in_off, flags, out_ptr, out_off)
+
+    def sha1_blocks_raw(self, nblocks, in_ptr, in_off):
+        """zpq_sha1_blocks on a caller buffer and offsets.  Returns (rc, the digests)."""
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        out = np.zeros(20 * nblocks + 1, dtype=np.uint8)
+        rc = lib().zpq_sha1_blocks(self.h, nblocks, in_ptr, in_off.ctypes.data, out.ctypes.data)
+        return rc, [out[20 * i:20 * i + 20].tobytes() for i in range(nblocks)]
+
+    def sha1_ranges_dev(self, nranges, d_in, d_begin, d_end, d_out20):
+        _ck(lib().zpq_sha1_ranges_dev(self.h, nranges, d_in, d_begin, d_end, d_out20), "zpq_sha1_ranges_dev")
+
+    def gather_dev(self, nblocks, d_src, d_src_off, d_len, d_dst, d_dst_off):
+        _ck(lib().zpq_gather_dev(self.h, nblocks, d_src, d_src_off, d_len, d_dst, d_dst_off), "zpq_gather_dev")
 
     def debug_contexts(self, model, data):
         n = model.ncomp
@@ -506,6 +565,18 @@ class BlockSet:
             "zpq_blockset_encode_segments")
         res = [out[int(out_off[i]):int(out_off[i]) + min(int(out_len[i]), caps[i])].tobytes() for i in range(n)]
         return res, status, out_len
+
+    def encode_segments_raw(self, members, in_ptr, in_off, flags, out_ptr, out_off):
+        """zpq_blockset_encode_segments on caller buffers and offsets (any window).  Returns (rc, out_len, status)."""
+        keep, mp = self._members(members, len(in_off) - 1)
+        return _enc_raw(lib().zpq_blockset_encode_segments, (self.h, len(in_off) - 1, mp), len(in_off) - 1, in_ptr, in_off,
+                        flags, out_ptr, out_off)
+
+    def decode_segments_raw(self, members, in_ptr, in_off, flags, out_ptr, out_off):
+        """zpq_blockset_decode_segments likewise.  Returns (rc, out_len, consumed, final_code, first_byte, status)."""
+        keep, mp = self._members(members, len(in_off) - 1)
+        return _dec_raw(lib().zpq_blockset_decode_segments, (self.h, len(in_off) - 1, mp), len(in_off) - 1, in_ptr, in_off,
+                        flags, out_ptr, out_off)
 
     def decode_segments(self, coded, cap, members=None, flags=FLAG_PP):
         n = len(coded)

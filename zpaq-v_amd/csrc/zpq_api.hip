@@ -653,19 +653,26 @@ static int host_batch(zpq_ctx *c, const zpq_model *m, int decode, int nblocks, c
     HIPCK(hipSetDevice(c->device));
     if (nblocks >= 2 && !own_slot && !trace && !ctx_out)
         return host_pipeline(c, m, decode, nblocks, in, in_off, flags, out, out_off, out_len, consumed, final_code, first_byte, status);
+    // One block (and the own_slot / trace / ctx_out forms): the window in[in_off[0] .. in_off[n]) alone goes up, the kernel
+    // sees offsets relative to it, and what it produced comes back to out + out_off[0] -- as host_pipeline does per round.
     int rc;
+    const uint64_t in_base = in_off[0], out_base = out_off[0];
+    const size_t win_in = (size_t)(in_off[nblocks] - in_base), win_out = (size_t)(out_off[nblocks] - out_base);
     const size_t offb = (size_t)(nblocks + 1) * 8, u32b = (size_t)nblocks * 4;
-    if ((rc = c->s_in.ensure(in_bytes + 16)) || (rc = c->s_out.ensure(out_bytes + 16)) ||
+    if ((rc = c->s_in.ensure(win_in + 16)) || (rc = c->s_out.ensure(win_out + 16)) ||
         (rc = c->s_inoff.ensure(offb)) || (rc = c->s_outoff.ensure(offb)) ||
         (rc = c->s_status.ensure(u32b)))
         return rc;
     for (auto &b : c->s_u32) if ((rc = b.ensure(u32b))) return rc;
     const size_t misc_bytes = (trace ? (size_t)ntrace * 4 : 0) + ctx_words * 4 + 16;
     if ((rc = c->s_misc.ensure(misc_bytes))) return rc;
+    std::vector<uint64_t> rel(2 * ((size_t)nblocks + 1));
+    uint64_t *const rel_in = rel.data(), *const rel_out = rel.data() + nblocks + 1;
+    for (int b = 0; b <= nblocks; b++) { rel_in[b] = in_off[b] - in_base; rel_out[b] = out_off[b] - out_base; }
     hipStream_t s = c->stream;
-    if (in_bytes) HIPCK(hipMemcpyAsync(c->s_in.p, in, in_bytes, hipMemcpyHostToDevice, s));
-    HIPCK(hipMemcpyAsync(c->s_inoff.p, in_off, offb, hipMemcpyHostToDevice, s));
-    HIPCK(hipMemcpyAsync(c->s_outoff.p, out_off, offb, hipMemcpyHostToDevice, s));
+    if (win_in) HIPCK(hipMemcpyAsync(c->s_in.p, in + in_base, win_in, hipMemcpyHostToDevice, s));
+    HIPCK(hipMemcpyAsync(c->s_inoff.p, rel_in, offb, hipMemcpyHostToDevice, s));
+    HIPCK(hipMemcpyAsync(c->s_outoff.p, rel_out, offb, hipMemcpyHostToDevice, s));
     HIPCK(hipMemsetAsync(c->s_status.p, 0xff, u32b, s));   // -1: "kernel never reported"
     HIPCK(hipMemsetAsync(c->s_u32[0].p, 0, u32b, s));
     if (misc_bytes > 16) HIPCK(hipMemsetAsync(c->s_misc.p, 0, misc_bytes, s));
@@ -688,12 +695,12 @@ static int host_batch(zpq_ctx *c, const zpq_model *m, int decode, int nblocks, c
     if (decode && consumed) HIPCK(hipMemcpyAsync(consumed, a.consumed, u32b, hipMemcpyDeviceToHost, s));
     if (decode && final_code) HIPCK(hipMemcpyAsync(final_code, a.final_code, u32b, hipMemcpyDeviceToHost, s));
     if (decode && first_byte) HIPCK(hipMemcpyAsync(first_byte, a.first_byte, u32b, hipMemcpyDeviceToHost, s));
-    if (out_bytes && nblocks == 1) {
+    if (win_out && nblocks == 1) {
         // one segment (zpq_block_*): its slab is sized for the worst case; move only what was produced
         HIPCK(hipStreamSynchronize(s));
-        const size_t got = out_len[0] < out_bytes ? out_len[0] : out_bytes;
-        if (got) HIPCK(hipMemcpyAsync(out, c->s_out.p, got, hipMemcpyDeviceToHost, s));
-    } else if (out_bytes) HIPCK(hipMemcpyAsync(out, c->s_out.p, out_bytes, hipMemcpyDeviceToHost, s));
+        const size_t got = out_len[0] < win_out ? out_len[0] : win_out;
+        if (got) HIPCK(hipMemcpyAsync(out + out_base, c->s_out.p, got, hipMemcpyDeviceToHost, s));
+    } else if (win_out) HIPCK(hipMemcpyAsync(out + out_base, c->s_out.p, win_out, hipMemcpyDeviceToHost, s));
     if (trace) HIPCK(hipMemcpyAsync(trace, c->s_misc.p, (size_t)ntrace * 4, hipMemcpyDeviceToHost, s));
     if (ctx_out) HIPCK(hipMemcpyAsync(ctx_out, c->s_misc.p, ctx_words * 4, hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
@@ -725,7 +732,7 @@ static void *pinned_device_ptr(const void *p)
 }
 
 __global__ void __launch_bounds__(256) k_gather(const uint8_t *src, const uint64_t *src_off, const uint32_t *len,
-                                                uint8_t *dst, const uint64_t *dst_off, int n, uint32_t skip);
+                                                uint8_t *dst, const uint64_t *dst_off, int n, uint32_t skip, int slabs);
 
 // Batches of two or more blocks through host pointers, in ROUNDS of at most the resident capacity: round r+1 is
 // uploaded and round r-1 downloaded while round r is coded (three streams, two staging sets).  What replaces the
@@ -883,7 +890,7 @@ static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, int nblocks
             if (out_dev_view) {
                 // the GPU packs each block's produced bytes straight into the caller's (pinned) slab
                 hipLaunchKernelGGL(k_gather, dim3(n), dim3(256), 0, c->s_d2h, (const uint8_t *)S.out.p, (const uint64_t *)S.outoff.p,
-                                   (const uint32_t *)d_len, out_dev_view, (const uint64_t *)S.dstoff.p, n, skip);
+                                   (const uint32_t *)d_len, out_dev_view, (const uint64_t *)S.dstoff.p, n, skip, 1);
                 HIPCK(hipGetLastError());
             } else {
                 // pageable destination: the runtime stages this copy and the call returns only when it has run, so
@@ -967,15 +974,22 @@ extern "C" int zpq_decode_blocks_multi(zpq_ctx *const *ctxs, int nctx, const zpq
 // boundary, then 16-byte stores fed by two aligned 16-byte loads funnel-shifted to the source's
 // misalignment, then the tail.
 // skip: leave out the first `skip` bytes of every block (they have been copied already)
+// slabs: src_off has n + 1 entries and block b holds at most src_off[b + 1] - src_off[b] bytes, whatever len[b] says
+// (host_pipeline: a block whose slab was too small reports the length it needed, or cap + 1)
 __global__ void __launch_bounds__(256) k_gather(const uint8_t *src, const uint64_t *src_off, const uint32_t *len,
-                                                uint8_t *dst, const uint64_t *dst_off, int n, uint32_t skip)
+                                                uint8_t *dst, const uint64_t *dst_off, int n, uint32_t skip, int slabs)
 {
     const int b = blockIdx.x;
     if (b >= n) return;
-    if (len[b] <= skip) return;
+    uint32_t have = len[b];
+    if (slabs) {
+        const uint64_t cap = src_off[b + 1] - src_off[b];
+        if (have > cap) have = (uint32_t)cap;
+    }
+    if (have <= skip) return;
     const uint8_t *s = src + src_off[b] + skip;
     uint8_t *d = dst + dst_off[b] + skip;
-    const uint32_t L = len[b] - skip;
+    const uint32_t L = have - skip;
     uint32_t head = (uint32_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(d) & 15u)) & 15u);
     if (head > L) head = L;
     for (uint32_t i = threadIdx.x; i < head; i += 256) d[i] = s[i];
@@ -1010,7 +1024,7 @@ extern "C" int zpq_gather_dev(zpq_ctx *c, int nblocks, const uint8_t *src, const
     if (nblocks == 0) return ZPQ_OK;
     if (!src_off || !len || !dst_off) return ZPQ_E_ARG;
     HIPCK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_gather, dim3(nblocks), dim3(256), 0, c->stream, src, src_off, len, dst, dst_off, nblocks, 0u);
+    hipLaunchKernelGGL(k_gather, dim3(nblocks), dim3(256), 0, c->stream, src, src_off, len, dst, dst_off, nblocks, 0u, 0);
     return hipGetLastError() == hipSuccess ? ZPQ_OK : ZPQ_E_INTERNAL;
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
