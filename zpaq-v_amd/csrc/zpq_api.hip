@@ -29,41 +29,7 @@
 #include "zpq_common.h"
 #include "zpq_host.h"
 
-extern "C" void zpq_launch_generic(const DBatch *B, const DModel *hostM, int decode, int grid, hipStream_t stream);
-extern "C" int zpq_generic_blocks_per_cu(const DModel *M);
-extern "C" int zpq_lanes_supported(const DModel *M);
-extern "C" int zpq_pipe_shape_applies(const DModel *M);   // zpq_pipe.hip: the chain is one of the shapes k_pipe codes
 #define ZPQ_SET_ALL (ZPQ_SET_LANES | ZPQ_SET_PIPE | ZPQ_SET_WAVES | ZPQ_SET_VMWAVES)
-extern "C" int zpq_launch_lanes_set_init(const DModel *d_model, const uint32_t *d_img, uint8_t *slots, int nmembers, hipStream_t stream);
-extern "C" int zpq_launch_lanes_keep(const DBatch *B, const DModel *hostM, int decode, hipStream_t stream);
-extern "C" int zpq_launch_wset(const DBatch *B, const DModel *hostM, int decode, hipStream_t stream, const char **name);   // ZPQ_SET_WAVES: k_wset / k_wsetd
-extern "C" int zpq_launch_vset(const DBatch *B, const DModel *hostM, int decode, hipStream_t stream, const char **name);   // ZPQ_SET_VMWAVES: k_vset / k_vsetd
-extern "C" int zpq_gpipe_shape_applies(const DModel *M);        // the envelopes of the wave kernels from the model's shape alone
-extern "C" int zpq_gdec_shape_applies(const DModel *M);
-extern "C" int zpq_lanes_blocks_per_cu(const DModel *M);
-extern "C" int zpq_launch_lanes(const DBatch *B, const DModel *hostM, int decode, int nslots, hipStream_t stream);
-extern "C" const char *zpq_lanes_kernel_name(const DModel *M, int decode);   // k_rows (four blocks per wave) or k_lanes
-// zpq_gpipe.hip: the ENCODER of general models as a pipeline of waves (wave = component, lane = block)
-extern "C" int zpq_gpipe_applies(const DModel *M);
-extern "C" int zpq_gpipe_blocks_per_cu(const DModel *M);
-extern "C" int zpq_launch_gpipe(const DBatch *B, const DModel *hostM, int nslots, hipStream_t stream);
-extern "C" int zpq_gdec_applies(const DModel *M);               // ... and their DECODER, bit-synchronous, a barrier per level of the prediction chain
-extern "C" int zpq_gdec_blocks_per_cu(const DModel *M);
-extern "C" int zpq_launch_gdec(const DBatch *B, const DModel *hostM, int nslots, hipStream_t stream);
-// ... and the same pair with an interpreter wave, for any other HCOMP program (on request: ZPQ_FLAG_VMPIPE / ZPQ_VM_PIPE)
-extern "C" int zpq_vpipe_applies(const DModel *M);
-extern "C" int zpq_vpipe_blocks_per_cu(const DModel *M);
-extern "C" int zpq_launch_vpipe(const DBatch *B, const DModel *hostM, int nslots, hipStream_t stream);
-extern "C" int zpq_vdec_applies(const DModel *M);
-extern "C" int zpq_vdec_blocks_per_cu(const DModel *M);
-extern "C" int zpq_launch_vdec(const DBatch *B, const DModel *hostM, int nslots, hipStream_t stream);
-extern "C" int zpq_chain_blocks_per_wg(const DModel *M);   // 0 = model not supported by the chain kernel
-extern "C" int zpq_chain_max_wgs(const DModel *M, int cus);
-extern "C" int zpq_chain_plan(const DModel *M, int nblocks, int cus, int *blocks_per_wg);
-extern "C" int zpq_launch_chain(const DBatch *B, const DModel *hostM, int decode, int nwg, int blocks_per_wg,
-                                hipStream_t stream, const char **name_out);
-extern "C" int zpq_chain_has_hio(const DModel *M);   // kernels that take part in striped host transfers exist for this model
-extern "C" int zpq_launch_sha1(const uint8_t *in, const uint64_t *beg, const uint64_t *end, int n, uint8_t *out20, hipStream_t stream);
 
 #define HIPCK(x)                                                              \
     do {                                                                      \
@@ -105,6 +71,112 @@ struct DevBuf {
         return ZPQ_OK;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }                                // (the owner has selected the device: zpq_ctx_destroy)
+};
+
+// The caller's arrays of a batch call, as include/zpaq_hip.h passes them: host pointers at the host entry points, device
+// pointers below run_batch.  consumed / final_code / first_byte are the decoder's and may be null.
+struct BlockArrays {
+    int n = 0;
+    const uint8_t *in = nullptr; const uint64_t *in_off = nullptr;
+    uint32_t flags = 0;
+    uint8_t *out = nullptr; const uint64_t *out_off = nullptr;
+    uint32_t *out_len = nullptr, *consumed = nullptr, *final_code = nullptr, *first_byte = nullptr;
+    int32_t *status = nullptr;
+    // blocks [b0, b1): the offsets stay absolute, so in / out do not move
+    BlockArrays window(int b0, int b1) const
+    {
+        BlockArrays w = *this;
+        w.n = b1 - b0; w.in_off = in_off + b0; w.out_off = out_off + b0; w.out_len = out_len + b0; w.status = status + b0;
+        w.consumed = consumed ? consumed + b0 : nullptr;
+        w.final_code = final_code ? final_code + b0 : nullptr;
+        w.first_byte = first_byte ? first_byte + b0 : nullptr;
+        return w;
+    }
+    uint64_t in_bytes() const { return in_off[n] - in_off[0]; }
+    uint64_t out_bytes() const { return out_off[n] - out_off[0]; }
+};
+// the ABI's parameter order, once (encoders have no consumed / final_code / first_byte)
+static BlockArrays block_arrays(int n, const uint8_t *in, const uint64_t *in_off, uint32_t flags, uint8_t *out, const uint64_t *out_off,
+                                uint32_t *out_len, int32_t *status, uint32_t *consumed = nullptr, uint32_t *final_code = nullptr,
+                                uint32_t *first_byte = nullptr)
+{
+    BlockArrays h;
+    h.n = n; h.in = in; h.in_off = in_off; h.flags = flags; h.out = out; h.out_off = out_off;
+    h.out_len = out_len; h.status = status; h.consumed = consumed; h.final_code = final_code; h.first_byte = first_byte;
+    return h;
+}
+// ... and what only the debug hooks and zpq_block pass
+struct BatchExtras {
+    uint8_t *own_slot = nullptr;   // zpq_block: use this slot instead of the pool
+    int32_t *trace = nullptr; uint32_t ntrace = 0;
+    uint32_t *ctx_out = nullptr; size_t ctx_words = 0;
+};
+
+// Slab check of a host-pointer call: offsets monotone, no block beyond what a 32-bit length holds, and bytes behind
+// every non-empty window.  `out` = false: the input half alone, without the length bound (zpq_sha1_blocks).
+static bool slabs_valid(const BlockArrays &h, bool out = true)
+{
+    for (int b = 0; b < h.n; b++) {
+        if (h.in_off[b + 1] < h.in_off[b]) return false;
+        if (out && (h.out_off[b + 1] < h.out_off[b] || h.in_off[b + 1] - h.in_off[b] > 0xFFFFFFF0ull ||
+                    h.out_off[b + 1] - h.out_off[b] > 0xFFFFFFF0ull))
+            return false;
+    }
+    return !(h.in_bytes() && !h.in) && !(out && h.out_bytes() && !h.out);
+}
+
+// One staging set for a window of host blocks: the device side of the bytes, the offsets and the small results, the
+// pinned host side of the small arrays, and the events that order a round's upload, kernel and download.  The ctx has
+// three: one for the one-shot calls, two for host_pipeline's rounds.
+struct StageSet {
+    DevBuf in, out, inoff, outoff, dstoff, meta, status, misc;   // misc: trace / ctx_out, or a block set's slot map
+    hipEvent_t ev_in = nullptr, ev_k = nullptr, ev_out = nullptr;
+    // pinned host side of the small arrays: a copy to or from PAGEABLE memory blocks the calling thread until it
+    // has run, i.e. until the round's kernel is done -- which would keep the next round's upload from being queued
+    uint64_t *h_off = nullptr;         // [3][n + 1]: relative in / out offsets, absolute destination offsets
+    uint32_t *h_meta = nullptr;        // [4][n] out_len, consumed, final_code, first_byte  + [n] status
+    size_t h_cap = 0;                  // blocks the pinned arrays are sized for
+    int b0 = 0, n = 0;                 // the window whose results sit in h_meta (not yet handed to the caller)
+    StageSet() = default;
+    StageSet(const StageSet &) = delete;
+    StageSet &operator=(const StageSet &) = delete;
+    ~StageSet()
+    {
+        if (h_off) (void)hipHostFree(h_off);
+        if (h_meta) (void)hipHostFree(h_meta);
+        for (hipEvent_t e : {ev_in, ev_k, ev_out}) if (e) (void)hipEventDestroy(e);
+    }
+    int create_events()
+    {
+        for (hipEvent_t *e : {&ev_in, &ev_k, &ev_out}) HIPCK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        return ZPQ_OK;
+    }
+    int ensure_host(size_t nblk)
+    {
+        if (nblk <= h_cap) return ZPQ_OK;
+        if (h_off) (void)hipHostFree(h_off);
+        if (h_meta) (void)hipHostFree(h_meta);
+        h_off = nullptr; h_meta = nullptr; h_cap = 0;
+        const size_t want = nblk + nblk / 8 + 16;
+        if (hipHostMalloc((void **)&h_off, 3 * (want + 1) * 8, hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc((void **)&h_meta, 5 * want * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return ZPQ_E_NOMEM; }
+        h_cap = want;
+        return ZPQ_OK;
+    }
+    uint64_t *h_in() const { return h_off; }
+    uint64_t *h_out(int nb) const { return h_off + (nb + 1); }
+    uint64_t *h_dst(int nb) const { return h_off + 2 * (size_t)(nb + 1); }
+    // what a kernel sees of a staged window of nb blocks
+    BlockArrays device_view(int nb, uint32_t flags, int decode) const
+    {
+        uint32_t *m = (uint32_t *)meta.p;
+        return block_arrays(nb, (const uint8_t *)in.p, (const uint64_t *)inoff.p, flags, (uint8_t *)out.p, (const uint64_t *)outoff.p, m,
+                            (int32_t *)status.p, decode ? m + nb : nullptr, decode ? m + 2 * (size_t)nb : nullptr, decode ? m + 3 * (size_t)nb : nullptr);
+    }
 };
 
 struct zpq_ctx {
@@ -125,31 +197,9 @@ struct zpq_ctx {
     unsigned last_host = 0;                // what host_pipeline did with the last host-pointer batch (zpq_ctx_last_host_transfer)
     uint32_t last_sp = 0;                  // line-store capacity the last launch ran with (0 = dense)
     const char *last_name = "";
-    // staging for the host-pointer entry points
-    DevBuf s_in, s_out, s_inoff, s_outoff, s_u32[4], s_status, s_misc;
-    // pipelined host batches (host_pipeline): two staging sets, a copy-in and a copy-out stream beside the compute stream
-    struct PipeSet {
-        DevBuf in, out, inoff, outoff, dstoff, meta, status;
-        hipEvent_t ev_in = nullptr, ev_k = nullptr, ev_out = nullptr;
-        // pinned host side of the small arrays: a copy to or from PAGEABLE memory blocks the calling thread until it
-        // has run, i.e. until the round's kernel is done -- which would keep the next round's upload from being queued
-        uint64_t *h_off = nullptr;         // [3][n + 1]: relative in / out offsets, absolute destination offsets
-        uint32_t *h_meta = nullptr;        // [4][n] out_len, consumed, final_code, first_byte  + [n] status
-        size_t h_cap = 0;                  // blocks the pinned arrays are sized for
-        int b0 = 0, n = 0;                 // the round whose results sit in h_meta (not yet handed to the caller)
-        int ensure_host(size_t nblk)
-        {
-            if (nblk <= h_cap) return ZPQ_OK;
-            if (h_off) (void)hipHostFree(h_off);
-            if (h_meta) (void)hipHostFree(h_meta);
-            h_off = nullptr; h_meta = nullptr; h_cap = 0;
-            const size_t want = nblk + nblk / 8 + 16;
-            if (hipHostMalloc((void **)&h_off, 3 * (want + 1) * 8, hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc((void **)&h_meta, 5 * want * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return ZPQ_E_NOMEM; }
-            h_cap = want;
-            return ZPQ_OK;
-        }
-    } pipe[2];
+    // staging for the host-pointer entry points: the one-shot calls' set, and for pipelined host batches (host_pipeline)
+    // two more with a copy-in and a copy-out stream beside the compute stream
+    StageSet one, pipe[2];
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     uint32_t *h_gate = nullptr;            // pinned, device-visible: "the rest of the striped upload has arrived"
     std::mutex mu;
@@ -258,11 +308,7 @@ static int ctx_init(zpq_ctx *c, const zpq::Tables &T)
     HIPCK(hipStreamCreateWithFlags(&c->s_d2h, hipStreamNonBlocking));
     HIPCK(hipHostMalloc((void **)&c->h_gate, 64, hipHostMallocPortable | hipHostMallocMapped));
     *c->h_gate = 1;
-    for (auto &ps : c->pipe) {
-        HIPCK(hipEventCreateWithFlags(&ps.ev_in, hipEventDisableTiming));
-        HIPCK(hipEventCreateWithFlags(&ps.ev_k, hipEventDisableTiming));
-        HIPCK(hipEventCreateWithFlags(&ps.ev_out, hipEventDisableTiming));
-    }
+    for (auto &ps : c->pipe) if (int rc = ps.create_events()) return rc;   // (the one-shot set runs on one stream: no events)
     // device tables: squash/stretch/dt2k narrowed to i16 (all values fit)
     std::vector<int16_t> sq(4096), st(32768), d2(256);
     for (int i = 0; i < 4096; i++) sq[i] = (int16_t)T.squash[i];
@@ -318,18 +364,6 @@ extern "C" void zpq_ctx_destroy(zpq_ctx *c) try
         c->set_bytes = 0;
     }
     for (auto &kv : c->models) { (void)hipFree(kv.second.d_model); (void)hipFree(kv.second.d_img); }
-    c->slots.release();
-    c->s_in.release(); c->s_out.release(); c->s_inoff.release(); c->s_outoff.release();
-    for (auto &b : c->s_u32) b.release();
-    c->s_status.release(); c->s_misc.release();
-    for (auto &ps : c->pipe) {
-        ps.in.release(); ps.out.release(); ps.inoff.release(); ps.outoff.release(); ps.dstoff.release(); ps.meta.release(); ps.status.release();
-        if (ps.h_off) (void)hipHostFree(ps.h_off);
-        if (ps.h_meta) (void)hipHostFree(ps.h_meta);
-        if (ps.ev_in) (void)hipEventDestroy(ps.ev_in);
-        if (ps.ev_k) (void)hipEventDestroy(ps.ev_k);
-        if (ps.ev_out) (void)hipEventDestroy(ps.ev_out);
-    }
     if (c->h_gate) (void)hipHostFree(c->h_gate);
     if (c->s_h2d) { (void)hipStreamSynchronize(c->s_h2d); (void)hipStreamDestroy(c->s_h2d); }
     if (c->s_d2h) { (void)hipStreamSynchronize(c->s_d2h); (void)hipStreamDestroy(c->s_d2h); }
@@ -338,7 +372,7 @@ extern "C" void zpq_ctx_destroy(zpq_ctx *c) try
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                               // (the slot pool and the staging sets release themselves: the device is selected above)
 } ZPQ_CATCH(return)
 
 extern "C" int zpq_ctx_sync(zpq_ctx *c) try
@@ -406,30 +440,81 @@ static int get_dev_model(zpq_ctx *c, const zpq_model *m, const DModel &layout, u
 
 // ------------------------------------------------------------------ batch core (device pointers)
 struct BatchArgs {
-    int nblocks;
-    const uint8_t *in; const uint64_t *in_off;
-    uint32_t flags;
-    uint8_t *out; const uint64_t *out_off;
-    uint32_t *out_len, *consumed, *final_code, *first_byte;
-    int32_t *status;
-    int32_t *trace; uint32_t ntrace;
-    uint32_t *ctx_out;
-    uint8_t *own_slot;   // zpq_block: use this slot instead of the pool
-    const uint32_t *gate_flag;   // striped upload (chain encode only): see DBatch
-    uint32_t gate_pos;
-    uint32_t *prog_counter;      // early download (chain decode only): see DBatch
-    uint32_t prog_pos;
+    BlockArrays io;                        // device pointers
+    BatchExtras x;                         // (trace and ctx_out device pointers too; ctx_words is the host's business)
+    const uint32_t *gate_flag = nullptr;   // striped upload (chain encode only): see DBatch
+    uint32_t gate_pos = 0;
+    uint32_t *prog_counter = nullptr;      // early download (chain decode only): see DBatch
+    uint32_t prog_pos = 0;
+};
+
+// ---- knobs: each parsed in one place, and read when the call is made
+// A request flag and its environment variable: NAME=1 sets the request for every call of the process, NAME=0 clears it,
+// anything but a leading '0' or '1' decides nothing (ZPQ_VM_PIPE, ZPQ_SET_LANES / _PIPE / _WAVES / _VMWAVES).
+static bool request(const char *var, uint32_t flags, uint32_t bit)
+{
+    const char *ev = getenv(var);
+    const bool env = ev && (ev[0] == '0' || ev[0] == '1');
+    return env ? ev[0] == '1' : (flags & bit) != 0;
+}
+struct SparseKnobs {
+    uint32_t forced_cap = 0;               // ZPQ_SPARSE_FORCE_LOG2 = 8 .. 25 (tests: exercise the store on small models), else 0
+    bool never = false, always = false;    // ZPQ_SPARSE_MODE, a tuning knob: "never" / "always" (a forced capacity is "always")
+};
+static SparseKnobs sparse_knobs()
+{
+    SparseKnobs k;
+    const char *ev = getenv("ZPQ_SPARSE_FORCE_LOG2");
+    const int lg = ev ? atoi(ev) : 0;
+    if (lg >= 8 && lg <= 25) k.forced_cap = 1u << lg;
+    const char *mode = getenv("ZPQ_SPARSE_MODE");
+    k.never = mode && !strcmp(mode, "never");
+    k.always = k.forced_cap || (mode && !strcmp(mode, "always"));
+    return k;
+}
+// a model the chain kernels take
+static bool is_chain_model(const zpq_model *m) { return m->d.fast_kind && zpq_chain_blocks_per_wg(&m->d) > 0; }
+
+// ---- the kernel families of a batch call
+enum Family {
+    F_CHAIN,                     // zpq_chain.hip (which chooses k_chain, k_pipe, k_dpipe ... itself)
+    F_GENERIC,                   // lane 0 runs every component: any model, own slots, traces
+    F_LANES,                     // up to 64 components: one block per wave, lane i = component i (k_rows / k_lanes)
+    F_GPIPE, F_GDEC,             // lanes family, encode / decode: the wave-per-component pipeline and its decoder (zpq_gpipe.hip)
+    F_VPIPE, F_VDEC,             // the same pair with an interpreter wave (k_vpipe / k_vdec), when asked for
+    F_COUNT
 };
 
 // What a batch call will launch: kernel family, slot layout, resident slots and grid.
 struct Plan {
-    bool chain = false, lanes = false;
-    bool gpipe = false;          // lanes family, encode: the wave-per-component pipeline (zpq_gpipe.hip)
-    bool gdec = false;           // lanes family, decode: the wave-per-component decoder (zpq_gpipe.hip, k_gdec)
-    bool vpipe = false, vdec = false;   // the same pair with an interpreter wave (k_vpipe / k_vdec), when asked for
+    Family fam = F_GENERIC;
     uint32_t sp = 0;             // compact line store capacity (lines), 0 = dense tables
-    const DModel *M = nullptr;   // layout the kernels see (dense or compact)
+    DModel M;                    // layout the kernels see (dense or compact): the plan's own copy
     int nslots = 0, grid = 0, bpw = 0;
+};
+
+// One row per family: the name zpq_ctx_last_kernel_name reports per direction (null: the launcher says), the resident
+// blocks per CU (null: the chain family plans its own grid, plan_chain) and the launcher behind one signature.
+struct FamilyRow {
+    const char *name[2];
+    int (*blocks_per_cu)(const DModel *M);
+    int (*launch)(const DBatch *B, const Plan &P, int decode, hipStream_t s, const char **name);
+};
+static const FamilyRow FAMILY[F_COUNT] = {
+    /* F_CHAIN   */ {{nullptr, nullptr}, nullptr,
+                     [](const DBatch *B, const Plan &P, int d, hipStream_t s, const char **n) { return zpq_launch_chain(B, &P.M, d, P.grid, P.bpw, s, n); }},
+    /* F_GENERIC */ {{"k_generic<encode>", "k_generic<decode>"}, zpq_generic_blocks_per_cu,
+                     [](const DBatch *B, const Plan &P, int d, hipStream_t s, const char **) { zpq_launch_generic(B, &P.M, d, P.grid, s); return (int)ZPQ_OK; }},
+    /* F_LANES   */ {{nullptr, nullptr}, zpq_lanes_blocks_per_cu,
+                     [](const DBatch *B, const Plan &P, int d, hipStream_t s, const char **n) { *n = zpq_lanes_kernel_name(&P.M, d); return zpq_launch_lanes(B, &P.M, d, P.nslots, s); }},
+    /* F_GPIPE   */ {{"k_gpipe<encode>", nullptr}, zpq_gpipe_blocks_per_cu,
+                     [](const DBatch *B, const Plan &P, int, hipStream_t s, const char **) { return zpq_launch_gpipe(B, &P.M, P.nslots, s); }},
+    /* F_GDEC    */ {{nullptr, "k_gdec<decode>"}, zpq_gdec_blocks_per_cu,
+                     [](const DBatch *B, const Plan &P, int, hipStream_t s, const char **) { return zpq_launch_gdec(B, &P.M, P.nslots, s); }},
+    /* F_VPIPE   */ {{"k_vpipe<encode>", nullptr}, zpq_vpipe_blocks_per_cu,
+                     [](const DBatch *B, const Plan &P, int, hipStream_t s, const char **) { return zpq_launch_vpipe(B, &P.M, P.nslots, s); }},
+    /* F_VDEC    */ {{nullptr, "k_vdec<decode>"}, zpq_vdec_blocks_per_cu,
+                     [](const DBatch *B, const Plan &P, int, hipStream_t s, const char **) { return zpq_launch_vdec(B, &P.M, P.nslots, s); }},
 };
 
 // resident slots / grid of the chain kernel for one slot layout
@@ -452,61 +537,56 @@ static int plan_chain(zpq_ctx *c, const DModel &M, int nblocks, int *nslots_out,
     return ZPQ_OK;
 }
 
-extern "C" int zpq_pipe_applies(const DModel *M, int blocks_per_wg, int nslots);   // the wave-pipelined encoder codes this plan
-
 static int plan_batch(zpq_ctx *c, const zpq_model *m, uint32_t flags, int nblocks, bool trace, bool own_slot, Plan *P, int decode = 0) try
 {
-    P->chain = m->d.fast_kind && !(flags & (ZPQ_FLAG_GENERIC | ZPQ_FLAG_LANES | ZPQ_FLAG_NOEOF | ZB_CTX_ONLY)) &&
-               !trace && !own_slot && zpq_chain_blocks_per_wg(&m->d) > 0;
-    static thread_local DModel sparse_layout;
-    P->sp = 0;
-    P->M = &m->d;
+    const bool pooled = !trace && !own_slot;
+    const bool chain = pooled && !(flags & (ZPQ_FLAG_GENERIC | ZPQ_FLAG_LANES | ZPQ_FLAG_NOEOF | ZB_CTX_ONLY)) && is_chain_model(m);
     // everything else with up to 64 components: one block per wave, lane i = component i
-    P->lanes = !P->chain && !(flags & (ZPQ_FLAG_GENERIC | ZPQ_FLAG_NOEOF | ZB_CTX_ONLY | ZB_KEEP_STATE)) &&
-               !trace && !own_slot && zpq_lanes_supported(&m->d);
+    const bool lanes = !chain && pooled && !(flags & (ZPQ_FLAG_GENERIC | ZPQ_FLAG_NOEOF | ZB_CTX_ONLY | ZB_KEEP_STATE)) &&
+                       zpq_lanes_supported(&m->d);
+    P->sp = 0;
+    P->M = m->d;
     int nslots, grid, bpw = 0;
-    if (P->chain) {
+    if (chain) {
         // Dense tables or the compact line store?  The store costs ~120 instructions per nibble and hashed
         // component, so it is used where it pays: when it lets the batch finish in fewer rounds of resident
         // blocks (levels 3-5 at scale, level 1 beyond ~6900 blocks), or when a dense slot is so large
         // (levels 4-5: 385 MiB / 2 GiB) that clearing it per block costs more than the store does.
+        P->fam = F_CHAIN;
         int dn = 0, dg = 0, db = 0;
         const int rcd = plan_chain(c, m->d, nblocks, &dn, &dg, &db);
-        const char *ev = getenv("ZPQ_SPARSE_FORCE_LOG2");        // tests: exercise the store on small models
-        const int lg = ev ? atoi(ev) : 0;
-        const bool forced = lg >= 8 && lg <= 25;
-        const uint32_t cap = forced ? (1u << lg) : c->sparse_cap;
-        const char *mode = getenv("ZPQ_SPARSE_MODE");            // tuning knob: "never" / "always"
-        const bool never = mode && !strcmp(mode, "never"), always = forced || (mode && !strcmp(mode, "always"));
+        const SparseKnobs K = sparse_knobs();
+        const uint32_t cap = K.forced_cap ? K.forced_cap : c->sparse_cap;
+        DModel sparse_layout;
         int sn = 0, sg = 0, sb = 0;
         bool use_sparse = false;
-        if (!never && zpq_sparse_layout(m->d, cap, &sparse_layout) && plan_chain(c, sparse_layout, nblocks, &sn, &sg, &sb) == ZPQ_OK) {
-            if (rcd != ZPQ_OK || always || m->d.slot_bytes > (256ull << 20)) use_sparse = true;
+        if (!K.never && zpq_sparse_layout(m->d, cap, &sparse_layout) && plan_chain(c, sparse_layout, nblocks, &sn, &sg, &sb) == ZPQ_OK) {
+            if (rcd != ZPQ_OK || K.always || m->d.slot_bytes > (256ull << 20)) use_sparse = true;
             else {
                 const int rounds_d = (nblocks + dn - 1) / dn, rounds_s = (nblocks + sn - 1) / sn;
                 use_sparse = rounds_s < rounds_d;
             }
         }
-        if (use_sparse) { P->sp = cap; P->M = &sparse_layout; nslots = sn; grid = sg; bpw = sb; }
+        if (use_sparse) { P->sp = cap; P->M = sparse_layout; nslots = sn; grid = sg; bpw = sb; }
         else {
             if (rcd != ZPQ_OK) return rcd;
             nslots = dn; grid = dg; bpw = db;
         }
     } else {
-        const DModel &M = *P->M;
+        const DModel &M = P->M;
         const uint64_t max_by_mem = M.slot_bytes ? (c->pool_budget() / M.slot_bytes) : (uint64_t)nblocks;
         if (max_by_mem == 0 && !own_slot) return ZPQ_E_NOMEM;
         nslots = nblocks;
-        P->gpipe = P->lanes && !decode && zpq_gpipe_applies(&M) != 0;
-        P->gdec = P->lanes && decode && zpq_gdec_applies(&M) != 0;
-        // ZPQ_FLAG_VMPIPE, a request: ZPQ_VM_PIPE=1 sets it for every call of the process, ZPQ_VM_PIPE=0 clears it
-        // (anything but a leading '0' or '1' decides nothing; a zpq_block's first segment keeps its kernel: ZB_NO_VMPIPE)
-        const char *vev = getenv("ZPQ_VM_PIPE");
-        const bool vm_env = vev && (vev[0] == '0' || vev[0] == '1');
-        const bool vm_pipe = !(flags & ZB_NO_VMPIPE) && (vm_env ? vev[0] == '1' : (flags & ZPQ_FLAG_VMPIPE) != 0);
-        P->vpipe = vm_pipe && P->lanes && !decode && !P->gpipe && zpq_vpipe_applies(&M) != 0;
-        P->vdec = vm_pipe && P->lanes && decode && !P->gdec && zpq_vdec_applies(&M) != 0;
-        const int cap_res = c->cus * (P->vpipe ? zpq_vpipe_blocks_per_cu(&M) : P->vdec ? zpq_vdec_blocks_per_cu(&M) : P->gpipe ? zpq_gpipe_blocks_per_cu(&M) : P->gdec ? zpq_gdec_blocks_per_cu(&M) : P->lanes ? zpq_lanes_blocks_per_cu(&M) : zpq_generic_blocks_per_cu(&M));
+        P->fam = F_GENERIC;
+        if (lanes) {
+            // the wave pipelines where the model is in their envelope; the pair with an interpreter wave only on request
+            // (ZPQ_FLAG_VMPIPE / ZPQ_VM_PIPE; a zpq_block's first segment keeps its kernel: ZB_NO_VMPIPE)
+            const bool vm_pipe = !(flags & ZB_NO_VMPIPE) && request("ZPQ_VM_PIPE", flags, ZPQ_FLAG_VMPIPE);
+            if ((decode ? zpq_gdec_applies(&M) : zpq_gpipe_applies(&M)) != 0) P->fam = decode ? F_GDEC : F_GPIPE;
+            else if (vm_pipe && (decode ? zpq_vdec_applies(&M) : zpq_vpipe_applies(&M)) != 0) P->fam = decode ? F_VDEC : F_VPIPE;
+            else P->fam = F_LANES;
+        }
+        const int cap_res = c->cus * FAMILY[P->fam].blocks_per_cu(&M);
         if (nslots > cap_res) nslots = cap_res;
         if (!own_slot && (uint64_t)nslots > max_by_mem) nslots = (int)max_by_mem;
         grid = nslots;
@@ -527,94 +607,87 @@ extern "C" int zpq_ctx_resident_capacity(zpq_ctx *c, const zpq_model *m, uint32_
     return rc != ZPQ_OK ? rc : (P.nslots < Q.nslots ? P.nslots : Q.nslots);
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
-static int run_batch(zpq_ctx *c, const zpq_model *m, int decode, const BatchArgs &a)
+// a DBatch with the model, its image, the ctx's tables and the (device) arrays of the call
+static DBatch batch_base(const zpq_ctx *c, const DevModel &dm, const BlockArrays &io)
 {
-    if (!ctx_live(c)) return c ? ZPQ_E_CLOSED : ZPQ_E_ARG;
-    if (!m) return ZPQ_E_ARG;
-    if (a.nblocks < 0) return ZPQ_E_ARG;
-    if (a.nblocks == 0) return ZPQ_OK;
-    if (!a.in_off || !a.out_off || !a.out_len || !a.status) return ZPQ_E_ARG;
-    if (a.own_slot && a.nblocks != 1) return ZPQ_E_ARG;
-    HIPCK(hipSetDevice(c->device));
-    Plan P;
-    int rc = plan_batch(c, m, a.flags, a.nblocks, a.trace != nullptr, a.own_slot != nullptr, &P, decode);
-    if (rc != ZPQ_OK) return rc;
-    const DModel &M = *P.M;
-    const bool want_chain = P.chain, want_lanes = P.lanes;
-    const int nslots = P.nslots, grid = P.grid, bpw = P.bpw;
-    DevModel dm;
-    rc = get_dev_model(c, m, M, P.sp, &dm);
-    if (rc != ZPQ_OK) return rc;
-
     DBatch B;
     memset(&B, 0, sizeof B);
     B.model = dm.d_model; B.img = dm.d_img;
-    B.nblocks = a.nblocks; B.flags = a.flags; B.ntrace = a.ntrace;
-    B.in = a.in; B.in_off = a.in_off; B.out = a.out; B.out_off = a.out_off;
-    B.out_len = a.out_len; B.consumed = a.consumed; B.final_code = a.final_code;
-    B.first_byte = a.first_byte; B.status = a.status; B.trace = a.trace; B.ctx_out = a.ctx_out;
     B.squash = c->d_squash; B.stretch = c->d_stretch; B.dt = c->d_dt; B.dt2k = c->d_dt2k;
     B.ns = c->d_ns; B.stretch_c = c->d_stretch_c;
-    B.gate_flag = (want_chain && !decode) ? a.gate_flag : nullptr;
+    B.nblocks = io.n; B.flags = io.flags;
+    B.in = io.in; B.in_off = io.in_off; B.out = io.out; B.out_off = io.out_off;
+    B.out_len = io.out_len; B.consumed = io.consumed; B.final_code = io.final_code;
+    B.first_byte = io.first_byte; B.status = io.status;
+    return B;
+}
+
+// a launch on stream s between the ctx's two timing events, with the last_* bookkeeping; launch(&name) queues it
+template <class F> static int timed_launch(zpq_ctx *c, hipStream_t s, F &&launch)
+{
+    HIPCK(hipEventRecord(c->ev0, s));
+    const char *name = nullptr;
+    const int rc = launch(&name);
+    if (rc != ZPQ_OK) return rc;
+    c->last_name = name;
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(c->ev1, s));
+    c->ev_valid = true;
+    return ZPQ_OK;
+}
+static int launch_family(zpq_ctx *c, const DBatch &B, const Plan &P, int decode, hipStream_t s)
+{
+    return timed_launch(c, s, [&](const char **name) {
+        *name = FAMILY[P.fam].name[decode];
+        return FAMILY[P.fam].launch(&B, P, decode, s, name);
+    });
+}
+
+static int run_batch(zpq_ctx *c, const zpq_model *m, int decode, const BatchArgs &a)
+{
+    const BlockArrays &io = a.io;
+    if (!ctx_live(c)) return c ? ZPQ_E_CLOSED : ZPQ_E_ARG;
+    if (!m) return ZPQ_E_ARG;
+    if (io.n < 0) return ZPQ_E_ARG;
+    if (io.n == 0) return ZPQ_OK;
+    if (!io.in_off || !io.out_off || !io.out_len || !io.status) return ZPQ_E_ARG;
+    if (a.x.own_slot && io.n != 1) return ZPQ_E_ARG;
+    HIPCK(hipSetDevice(c->device));
+    Plan P;
+    int rc = plan_batch(c, m, io.flags, io.n, a.x.trace != nullptr, a.x.own_slot != nullptr, &P, decode);
+    if (rc != ZPQ_OK) return rc;
+    DevModel dm;
+    rc = get_dev_model(c, m, P.M, P.sp, &dm);
+    if (rc != ZPQ_OK) return rc;
+
+    DBatch B = batch_base(c, dm, io);
+    B.trace = a.x.trace; B.ntrace = a.x.ntrace; B.ctx_out = a.x.ctx_out;
+    B.gate_flag = (P.fam == F_CHAIN && !decode) ? a.gate_flag : nullptr;
     B.gate_pos = a.gate_pos;
     if (a.gate_flag && !B.gate_flag) return ZPQ_E_INTERNAL;      // (a gated upload must meet a kernel that honours the gate)
-    B.prog_counter = (want_chain && decode) ? a.prog_counter : nullptr;   // (other kernels do not report: the host then copies after the kernel)
+    B.prog_counter = (P.fam == F_CHAIN && decode) ? a.prog_counter : nullptr;   // (other kernels do not report: the host then copies after the kernel)
     B.prog_pos = a.prog_pos;
 
-    if (a.own_slot) {
-        B.slots = a.own_slot;
+    if (a.x.own_slot) {
+        B.slots = a.x.own_slot;
     } else {
-        rc = c->slots.ensure((size_t)nslots * M.slot_bytes + 256);   // (the slack a MIX row read needs is part of slot_bytes: zpq_model.cpp mix_row_pad)
+        rc = c->slots.ensure((size_t)P.nslots * P.M.slot_bytes + 256);   // (the slack a MIX row read needs is part of slot_bytes: zpq_model.cpp mix_row_pad)
         if (rc != ZPQ_OK) return rc;
         B.slots = (uint8_t *)c->slots.p;
     }
-    B.nslots = nslots;
-    c->last_slots = nslots;
+    B.nslots = P.nslots;
+    c->last_slots = P.nslots;
     c->last_sp = P.sp;
     c->last_host = 0;                                            // (host_pipeline sets it when its batch is through)
-
-    HIPCK(hipEventRecord(c->ev0, c->stream));
-    if (want_chain && !a.own_slot) {
-        const char *name = nullptr;
-        rc = zpq_launch_chain(&B, &M, decode, grid, bpw, c->stream, &name);
-        if (rc != ZPQ_OK) return rc;
-        c->last_name = name;
-    } else if (want_lanes && P.vpipe) {
-        rc = zpq_launch_vpipe(&B, &M, nslots, c->stream);
-        if (rc != ZPQ_OK) return rc;
-        c->last_name = "k_vpipe<encode>";
-    } else if (want_lanes && P.vdec) {
-        rc = zpq_launch_vdec(&B, &M, nslots, c->stream);
-        if (rc != ZPQ_OK) return rc;
-        c->last_name = "k_vdec<decode>";
-    } else if (want_lanes && P.gpipe) {
-        rc = zpq_launch_gpipe(&B, &M, nslots, c->stream);
-        if (rc != ZPQ_OK) return rc;
-        c->last_name = "k_gpipe<encode>";
-    } else if (want_lanes && P.gdec) {
-        rc = zpq_launch_gdec(&B, &M, nslots, c->stream);
-        if (rc != ZPQ_OK) return rc;
-        c->last_name = "k_gdec<decode>";
-    } else if (want_lanes) {
-        rc = zpq_launch_lanes(&B, &M, decode, nslots, c->stream);
-        if (rc != ZPQ_OK) return rc;
-        c->last_name = zpq_lanes_kernel_name(&M, decode);
-    } else {
-        zpq_launch_generic(&B, &M, decode, grid, c->stream);
-        c->last_name = decode ? "k_generic<decode>" : "k_generic<encode>";
-    }
-    HIPCK(hipGetLastError());
-    HIPCK(hipEventRecord(c->ev1, c->stream));
-    c->ev_valid = true;
-    return ZPQ_OK;
+    return launch_family(c, B, P, decode, c->stream);
 }
 
 extern "C" int zpq_encode_blocks_dev(zpq_ctx *c, const zpq_model *m, int nblocks, const uint8_t *in,
                                      const uint64_t *in_off, uint32_t flags, uint8_t *out,
                                      const uint64_t *out_off, uint32_t *out_len, int32_t *status) try
 {
-    BatchArgs a = {nblocks, in, in_off, flags & 0xffu, out, out_off, out_len, nullptr, nullptr, nullptr,
-                   status, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, 0};
+    BatchArgs a;
+    a.io = block_arrays(nblocks, in, in_off, flags & 0xffu, out, out_off, out_len, status);
     return run_batch(c, m, 0, a);
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
@@ -623,87 +696,107 @@ extern "C" int zpq_decode_blocks_dev(zpq_ctx *c, const zpq_model *m, int nblocks
                                      const uint64_t *out_off, uint32_t *out_len, uint32_t *consumed,
                                      uint32_t *final_code, uint32_t *first_byte, int32_t *status) try
 {
-    BatchArgs a = {nblocks, in, in_off, flags & 0xffu, out, out_off, out_len, consumed, final_code,
-                   first_byte, status, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, 0};
+    BatchArgs a;
+    a.io = block_arrays(nblocks, in, in_off, flags & 0xffu, out, out_off, out_len, status, consumed, final_code, first_byte);
     return run_batch(c, m, 1, a);
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 // ------------------------------------------------------------------ host-pointer forms
-static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, int nblocks, const uint8_t *in, const uint64_t *in_off,
-                         uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, uint32_t *consumed,
-                         uint32_t *final_code, uint32_t *first_byte, int32_t *status);
-static int host_batch(zpq_ctx *c, const zpq_model *m, int decode, int nblocks, const uint8_t *in,
-                      const uint64_t *in_off, uint32_t flags, uint8_t *out, const uint64_t *out_off,
-                      uint32_t *out_len, uint32_t *consumed, uint32_t *final_code,
-                      uint32_t *first_byte, int32_t *status, uint8_t *own_slot, int32_t *trace,
-                      uint32_t ntrace, uint32_t *ctx_out, size_t ctx_words)
+// Staging a window of nb blocks in a set, in three steps with the caller's upload of the bytes between the last two:
+// room on both sides; the offsets relative to the window (stage_offsets, or the caller's own packing); then the
+// offsets go up, status := -1 and the results := 0.
+static int stage_room(StageSet &S, int nb, size_t in_bytes, size_t out_bytes, size_t misc_bytes)
+{
+    int rc;
+    const size_t offb = (size_t)(nb + 1) * 8, u32b = (size_t)nb * 4;
+    if ((rc = S.in.ensure(in_bytes + 16)) || (rc = S.out.ensure(out_bytes + 16)) || (rc = S.inoff.ensure(offb)) ||
+        (rc = S.outoff.ensure(offb)) || (rc = S.dstoff.ensure(offb)) || (rc = S.meta.ensure(u32b * 4)) || (rc = S.status.ensure(u32b)) ||
+        (rc = S.misc.ensure(misc_bytes)) || (rc = S.ensure_host((size_t)nb)))
+        return rc;
+    return ZPQ_OK;
+}
+static void stage_offsets(StageSet &S, const BlockArrays &h)
+{
+    uint64_t *h_in = S.h_in(), *h_out = S.h_out(h.n), *h_dst = S.h_dst(h.n);
+    for (int k = 0; k <= h.n; k++) { h_in[k] = h.in_off[k] - h.in_off[0]; h_out[k] = h.out_off[k] - h.out_off[0]; h_dst[k] = h.out_off[k]; }
+}
+// dst: the absolute destination offsets as well (k_gather packs into the caller's slabs)
+static int stage_upload(StageSet &S, int nb, hipStream_t s, bool dst)
+{
+    const size_t offb = (size_t)(nb + 1) * 8, u32b = (size_t)nb * 4;
+    HIPCK(hipMemcpyAsync(S.inoff.p, S.h_in(), offb, hipMemcpyHostToDevice, s));
+    HIPCK(hipMemcpyAsync(S.outoff.p, S.h_out(nb), offb, hipMemcpyHostToDevice, s));
+    if (dst) HIPCK(hipMemcpyAsync(S.dstoff.p, S.h_dst(nb), offb, hipMemcpyHostToDevice, s));
+    HIPCK(hipMemsetAsync(S.status.p, 0xff, u32b, s));          // -1: "kernel never reported"
+    HIPCK(hipMemsetAsync(S.meta.p, 0, u32b * 4, s));
+    return ZPQ_OK;
+}
+// Handing the small results back: queue their download into the set's pinned arrays ...
+static int fetch_results(StageSet &S, int b0, int nb, hipStream_t s)
+{
+    HIPCK(hipMemcpyAsync(S.h_meta, S.meta.p, (size_t)nb * 16, hipMemcpyDeviceToHost, s));
+    HIPCK(hipMemcpyAsync(S.h_meta + 4 * (size_t)nb, S.status.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+    S.b0 = b0; S.n = nb;
+    return ZPQ_OK;
+}
+// ... and, once that has run, give them to the caller's arrays: the window's block j is the caller's at[j] (null: b0 + j)
+static void deliver(StageSet &S, const BlockArrays &h, int decode, const int *at = nullptr)
+{
+    const size_t nn = (size_t)S.n;
+    for (size_t j = 0; j < nn; j++) {
+        const size_t i = at ? (size_t)at[j] : (size_t)S.b0 + j;
+        h.out_len[i] = S.h_meta[j];
+        if (decode && h.consumed) h.consumed[i] = S.h_meta[nn + j];
+        if (decode && h.final_code) h.final_code[i] = S.h_meta[2 * nn + j];
+        if (decode && h.first_byte) h.first_byte[i] = S.h_meta[3 * nn + j];
+        h.status[i] = (int32_t)S.h_meta[4 * nn + j];
+    }
+    S.n = 0;
+}
+
+static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, const BlockArrays &h);
+static int host_batch(zpq_ctx *c, const zpq_model *m, int decode, const BlockArrays &h, const BatchExtras &x = BatchExtras())
 {
     if (!ctx_live(c)) return c ? ZPQ_E_CLOSED : ZPQ_E_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     c->last_host = 0;                                            // (whatever becomes of this call: host_pipeline sets it at its end)
-    if (!m || nblocks < 0) return ZPQ_E_ARG;
-    if (nblocks == 0) return ZPQ_OK;
-    if (!in_off || !out_off || !out_len || !status) return ZPQ_E_ARG;
-    for (int b = 0; b < nblocks; b++)
-        if (in_off[b + 1] < in_off[b] || out_off[b + 1] < out_off[b] ||
-            in_off[b + 1] - in_off[b] > 0xFFFFFFF0ull || out_off[b + 1] - out_off[b] > 0xFFFFFFF0ull)
-            return ZPQ_E_ARG;
-    const size_t in_bytes = (size_t)in_off[nblocks], out_bytes = (size_t)out_off[nblocks];
-    if ((in_bytes && !in) || (out_bytes && !out)) return ZPQ_E_ARG;
+    if (!m || h.n < 0) return ZPQ_E_ARG;
+    if (h.n == 0) return ZPQ_OK;
+    if (!h.in_off || !h.out_off || !h.out_len || !h.status) return ZPQ_E_ARG;
+    if (!slabs_valid(h)) return ZPQ_E_ARG;
     HIPCK(hipSetDevice(c->device));
-    if (nblocks >= 2 && !own_slot && !trace && !ctx_out)
-        return host_pipeline(c, m, decode, nblocks, in, in_off, flags, out, out_off, out_len, consumed, final_code, first_byte, status);
+    if (h.n >= 2 && !x.own_slot && !x.trace && !x.ctx_out) return host_pipeline(c, m, decode, h);
     // One block (and the own_slot / trace / ctx_out forms): the window in[in_off[0] .. in_off[n]) alone goes up, the kernel
     // sees offsets relative to it, and what it produced comes back to out + out_off[0] -- as host_pipeline does per round.
-    int rc;
-    const uint64_t in_base = in_off[0], out_base = out_off[0];
-    const size_t win_in = (size_t)(in_off[nblocks] - in_base), win_out = (size_t)(out_off[nblocks] - out_base);
-    const size_t offb = (size_t)(nblocks + 1) * 8, u32b = (size_t)nblocks * 4;
-    if ((rc = c->s_in.ensure(win_in + 16)) || (rc = c->s_out.ensure(win_out + 16)) ||
-        (rc = c->s_inoff.ensure(offb)) || (rc = c->s_outoff.ensure(offb)) ||
-        (rc = c->s_status.ensure(u32b)))
-        return rc;
-    for (auto &b : c->s_u32) if ((rc = b.ensure(u32b))) return rc;
-    const size_t misc_bytes = (trace ? (size_t)ntrace * 4 : 0) + ctx_words * 4 + 16;
-    if ((rc = c->s_misc.ensure(misc_bytes))) return rc;
-    std::vector<uint64_t> rel(2 * ((size_t)nblocks + 1));
-    uint64_t *const rel_in = rel.data(), *const rel_out = rel.data() + nblocks + 1;
-    for (int b = 0; b <= nblocks; b++) { rel_in[b] = in_off[b] - in_base; rel_out[b] = out_off[b] - out_base; }
+    StageSet &S = c->one;
     hipStream_t s = c->stream;
-    if (win_in) HIPCK(hipMemcpyAsync(c->s_in.p, in + in_base, win_in, hipMemcpyHostToDevice, s));
-    HIPCK(hipMemcpyAsync(c->s_inoff.p, rel_in, offb, hipMemcpyHostToDevice, s));
-    HIPCK(hipMemcpyAsync(c->s_outoff.p, rel_out, offb, hipMemcpyHostToDevice, s));
-    HIPCK(hipMemsetAsync(c->s_status.p, 0xff, u32b, s));   // -1: "kernel never reported"
-    HIPCK(hipMemsetAsync(c->s_u32[0].p, 0, u32b, s));
-    if (misc_bytes > 16) HIPCK(hipMemsetAsync(c->s_misc.p, 0, misc_bytes, s));
+    const size_t win_in = (size_t)h.in_bytes(), win_out = (size_t)h.out_bytes();
+    const size_t misc_bytes = (x.trace ? (size_t)x.ntrace * 4 : 0) + x.ctx_words * 4 + 16;
+    int rc = stage_room(S, h.n, win_in, win_out, misc_bytes);
+    if (rc != ZPQ_OK) return rc;
+    stage_offsets(S, h);
+    if (win_in) HIPCK(hipMemcpyAsync(S.in.p, h.in + h.in_off[0], win_in, hipMemcpyHostToDevice, s));
+    if ((rc = stage_upload(S, h.n, s, false)) != ZPQ_OK) return rc;
+    if (misc_bytes > 16) HIPCK(hipMemsetAsync(S.misc.p, 0, misc_bytes, s));
     BatchArgs a;
-    memset(&a, 0, sizeof a);
-    a.nblocks = nblocks; a.in = (const uint8_t *)c->s_in.p; a.in_off = (const uint64_t *)c->s_inoff.p;
-    a.flags = flags; a.out = (uint8_t *)c->s_out.p; a.out_off = (const uint64_t *)c->s_outoff.p;
-    a.out_len = (uint32_t *)c->s_u32[0].p;
-    a.consumed = decode ? (uint32_t *)c->s_u32[1].p : nullptr;
-    a.final_code = decode ? (uint32_t *)c->s_u32[2].p : nullptr;
-    a.first_byte = decode ? (uint32_t *)c->s_u32[3].p : nullptr;
-    a.status = (int32_t *)c->s_status.p;
-    a.own_slot = own_slot;
-    if (trace) { a.trace = (int32_t *)c->s_misc.p; a.ntrace = ntrace; }
-    if (ctx_out) a.ctx_out = (uint32_t *)c->s_misc.p;
+    a.io = S.device_view(h.n, h.flags, decode);
+    a.x.own_slot = x.own_slot;
+    if (x.trace) { a.x.trace = (int32_t *)S.misc.p; a.x.ntrace = x.ntrace; }
+    if (x.ctx_out) a.x.ctx_out = (uint32_t *)S.misc.p;
     rc = run_batch(c, m, decode, a);
     if (rc != ZPQ_OK) return rc;
-    HIPCK(hipMemcpyAsync(out_len, a.out_len, u32b, hipMemcpyDeviceToHost, s));
-    HIPCK(hipMemcpyAsync(status, a.status, u32b, hipMemcpyDeviceToHost, s));
-    if (decode && consumed) HIPCK(hipMemcpyAsync(consumed, a.consumed, u32b, hipMemcpyDeviceToHost, s));
-    if (decode && final_code) HIPCK(hipMemcpyAsync(final_code, a.final_code, u32b, hipMemcpyDeviceToHost, s));
-    if (decode && first_byte) HIPCK(hipMemcpyAsync(first_byte, a.first_byte, u32b, hipMemcpyDeviceToHost, s));
-    if (win_out && nblocks == 1) {
+    if ((rc = fetch_results(S, 0, h.n, s)) != ZPQ_OK) return rc;
+    uint8_t *const dst = win_out ? h.out + h.out_off[0] : nullptr;
+    if (win_out && h.n == 1) {
         // one segment (zpq_block_*): its slab is sized for the worst case; move only what was produced
         HIPCK(hipStreamSynchronize(s));
-        const size_t got = out_len[0] < win_out ? out_len[0] : win_out;
-        if (got) HIPCK(hipMemcpyAsync(out + out_base, c->s_out.p, got, hipMemcpyDeviceToHost, s));
-    } else if (win_out) HIPCK(hipMemcpyAsync(out + out_base, c->s_out.p, win_out, hipMemcpyDeviceToHost, s));
-    if (trace) HIPCK(hipMemcpyAsync(trace, c->s_misc.p, (size_t)ntrace * 4, hipMemcpyDeviceToHost, s));
-    if (ctx_out) HIPCK(hipMemcpyAsync(ctx_out, c->s_misc.p, ctx_words * 4, hipMemcpyDeviceToHost, s));
+        const size_t got = S.h_meta[0] < win_out ? S.h_meta[0] : win_out;
+        if (got) HIPCK(hipMemcpyAsync(dst, S.out.p, got, hipMemcpyDeviceToHost, s));
+    } else if (win_out) HIPCK(hipMemcpyAsync(dst, S.out.p, win_out, hipMemcpyDeviceToHost, s));
+    if (x.trace) HIPCK(hipMemcpyAsync(x.trace, S.misc.p, (size_t)x.ntrace * 4, hipMemcpyDeviceToHost, s));
+    if (x.ctx_out) HIPCK(hipMemcpyAsync(x.ctx_out, S.misc.p, x.ctx_words * 4, hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
+    deliver(S, h, decode);
     return ZPQ_OK;
 }
 
@@ -740,37 +833,28 @@ __global__ void __launch_bounds__(256) k_gather(const uint8_t *src, const uint64
 // block but moves the three phases of different rounds in parallel.  With PINNED caller buffers (zpq_host_alloc)
 // uploads are plain DMA and the output is packed by the GPU straight into the caller's slabs -- only bytes that
 // were produced cross PCIe; with pageable buffers the runtime's staged copies are used and whole slabs come back.
-static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, int nblocks, const uint8_t *in, const uint64_t *in_off,
-                         uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, uint32_t *consumed,
-                         uint32_t *final_code, uint32_t *first_byte, int32_t *status)
+static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, const BlockArrays &h)
 {
+    const int nblocks = h.n;
+    const uint8_t *const in = h.in;
+    uint8_t *const out = h.out;
     HIPCK(hipSetDevice(c->device));
     c->last_host = 0;
     Plan P0;
-    int rc = plan_batch(c, m, flags, nblocks, false, false, &P0, decode);
+    int rc = plan_batch(c, m, h.flags, nblocks, false, false, &P0, decode);
     if (rc != ZPQ_OK) return rc;
+    // striped upload / early download: a single round of the dense short chains (the kernels that honour the gate)
+    const bool hio = P0.fam == F_CHAIN && !P0.sp && zpq_chain_has_hio(&m->d) && !getenv("ZPQ_NO_STRIPE");
     // Rounds only where overlapping transfers with coding can pay: a batch that exceeds the resident capacity AND
     // moves a sizeable amount of data.  Smaller batches go as one launch (blocks beyond the capacity are worked off
     // by the resident groups in turn, inside the kernel).
     uint64_t min_bytes = 64ull << 20;
     if (const char *ev = getenv("ZPQ_PIPE_MIN_BYTES")) min_bytes = strtoull(ev, nullptr, 0);   // tests: force rounds on small data
-    const bool big = in_off[nblocks] - in_off[0] + out_off[nblocks] - out_off[0] >= min_bytes;
+    const bool big = h.in_bytes() + h.out_bytes() >= min_bytes;
     const int per_round = (big && P0.nslots > 0) ? P0.nslots : nblocks;
     uint8_t *const out_dev_view = (uint8_t *)pinned_device_ptr(out);           // non-null: the GPU can write the caller's slabs
-    const bool in_pinned = pinned_device_ptr(in) != nullptr;
-    (void)in_pinned;                                                            // (hipMemcpyAsync takes either kind; pinned = true DMA)
+    const bool in_pinned = pinned_device_ptr(in) != nullptr;                    // (hipMemcpyAsync takes either kind; pinned = true DMA)
     const int nrounds = (nblocks + per_round - 1) / per_round;
-    // hand a finished round's small results (in the set's pinned arrays) to the caller's arrays
-    auto deliver = [&](zpq_ctx::PipeSet &S) {
-        if (!S.n) return;
-        const size_t nn = (size_t)S.n;
-        memcpy(out_len + S.b0, S.h_meta, nn * 4);
-        if (decode && consumed) memcpy(consumed + S.b0, S.h_meta + nn, nn * 4);
-        if (decode && final_code) memcpy(final_code + S.b0, S.h_meta + 2 * nn, nn * 4);
-        if (decode && first_byte) memcpy(first_byte + S.b0, S.h_meta + 3 * nn, nn * 4);
-        memcpy(status + S.b0, S.h_meta + 4 * nn, nn * 4);
-        S.n = 0;
-    };
     c->pipe[0].n = c->pipe[1].n = 0;
     const uint32_t *gate_flag_dev = nullptr;
     uint64_t stripe_L = 0, early_L = 0;
@@ -781,18 +865,14 @@ static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, int nblocks
         stripe_delay_us = v > 500000ull ? 500000u : (uint32_t)v;
     }
     for (int r = 0; r < nrounds; r++) {
-        zpq_ctx::PipeSet &S = c->pipe[r & 1];
+        StageSet &S = c->pipe[r & 1];
         const int b0 = r * per_round, b1 = (b0 + per_round < nblocks) ? b0 + per_round : nblocks, n = b1 - b0;
-        if (r >= 2) { HIPCK(hipEventSynchronize(S.ev_out)); deliver(S); }       // the set's previous round has left the device
-        const uint64_t in_base = in_off[b0], in_bytes = in_off[b1] - in_base;
-        const uint64_t out_base = out_off[b0], out_bytes = out_off[b1] - out_base;
-        const size_t offb = (size_t)(n + 1) * 8, u32b = (size_t)n * 4;
-        if ((rc = S.in.ensure(in_bytes + 16)) || (rc = S.out.ensure(out_bytes + 16)) || (rc = S.inoff.ensure(offb)) ||
-            (rc = S.outoff.ensure(offb)) || (rc = S.dstoff.ensure(offb)) || (rc = S.meta.ensure(u32b * 4)) || (rc = S.status.ensure(u32b)) ||
-            (rc = S.ensure_host((size_t)n)))
-            return rc;
-        uint64_t *h_in = S.h_off, *h_out = S.h_off + (n + 1), *h_dst = S.h_off + 2 * (size_t)(n + 1);
-        for (int k = 0; k <= n; k++) { h_in[k] = in_off[b0 + k] - in_base; h_out[k] = out_off[b0 + k] - out_base; h_dst[k] = out_off[b0 + k]; }
+        if (r >= 2) { HIPCK(hipEventSynchronize(S.ev_out)); deliver(S, h, decode); }   // the set's previous round has left the device
+        const BlockArrays w = h.window(b0, b1);
+        const uint64_t in_base = w.in_off[0], in_bytes = w.in_bytes(), out_base = w.out_off[0], out_bytes = w.out_bytes();
+        if ((rc = stage_room(S, n, in_bytes, out_bytes, 0)) != ZPQ_OK) return rc;
+        stage_offsets(S, w);
+        const uint64_t *h_in = S.h_in(), *h_out = S.h_out(n);
         // ---- upload on the copy-in stream
         // One round cannot overlap its upload with its own coding by rounds -- every block starts at once.  But an
         // encoder needs a block's bytes only as it gets to them (64 KiB take ~200 ms), so for a single round of equally
@@ -800,7 +880,7 @@ static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, int nblocks
         // starts, the rest follows while it runs; a lane that reaches the end of the first stripe waits for *h_gate.
         bool striped = false;
         const uint64_t stripe = 8192;
-        if (!decode && nrounds == 1 && in_pinned && P0.chain && !P0.sp && zpq_chain_has_hio(&m->d) && n >= 64 && !getenv("ZPQ_NO_STRIPE")) {
+        if (!decode && nrounds == 1 && in_pinned && hio && n >= 64) {
             const uint64_t L = h_in[1] - h_in[0];
             striped = L >= 4 * stripe && (L & 3u) == 0;
             for (int k = 1; k < n && striped; k++) striped = h_in[k + 1] - h_in[k] == L;
@@ -816,28 +896,19 @@ static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, int nblocks
             }
         }
         if (!striped && in_bytes) HIPCK(hipMemcpyAsync(S.in.p, in + in_base, in_bytes, hipMemcpyHostToDevice, c->s_h2d));
-        HIPCK(hipMemcpyAsync(S.inoff.p, h_in, offb, hipMemcpyHostToDevice, c->s_h2d));
-        HIPCK(hipMemcpyAsync(S.outoff.p, h_out, offb, hipMemcpyHostToDevice, c->s_h2d));
-        HIPCK(hipMemcpyAsync(S.dstoff.p, h_dst, offb, hipMemcpyHostToDevice, c->s_h2d));
-        HIPCK(hipMemsetAsync(S.status.p, 0xff, u32b, c->s_h2d));              // -1: "kernel never reported"
-        HIPCK(hipMemsetAsync(S.meta.p, 0, u32b * 4, c->s_h2d));
+        if ((rc = stage_upload(S, n, c->s_h2d, true)) != ZPQ_OK) return rc;
         HIPCK(hipEventRecord(S.ev_in, c->s_h2d));
         // ---- code on the compute stream
         HIPCK(hipStreamWaitEvent(c->stream, S.ev_in, 0));
-        uint32_t *d_len = (uint32_t *)S.meta.p, *d_cons = d_len + n, *d_code = d_cons + n, *d_first = d_code + n;
         BatchArgs a;
-        memset(&a, 0, sizeof a);
-        a.nblocks = n; a.in = (const uint8_t *)S.in.p; a.in_off = (const uint64_t *)S.inoff.p; a.flags = flags;
-        a.out = (uint8_t *)S.out.p; a.out_off = (const uint64_t *)S.outoff.p; a.out_len = d_len;
-        a.consumed = decode ? d_cons : nullptr; a.final_code = decode ? d_code : nullptr; a.first_byte = decode ? d_first : nullptr;
-        a.status = (int32_t *)S.status.p;
+        a.io = S.device_view(n, h.flags, decode);
         if (striped) { a.gate_flag = gate_flag_dev; a.gate_pos = (uint32_t)stripe; }
         // The mirror image for a decoder's output: every block reports when its first `early` bytes are stored (and
         // visible to the copy engines); once all have, that stripe is copied out beside the kernel, which still has
         // the last quarter of every block to decode.  Single round, pinned slabs of equal length and stride.
         uint32_t early = 0;
         uint32_t *prog_dev = nullptr;
-        if (decode && nrounds == 1 && out_dev_view && P0.chain && !P0.sp && zpq_chain_has_hio(&m->d) && n >= 64 && !getenv("ZPQ_NO_STRIPE")) {
+        if (decode && nrounds == 1 && out_dev_view && hio && n >= 64) {
             const uint64_t L = h_out[1] - h_out[0];
             bool uni = L >= 16384 && L <= 0x7FFFFFFFull;
             for (int k = 1; k < n && uni; k++) uni = h_out[k + 1] - h_out[k] == L;
@@ -883,14 +954,12 @@ static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, int nblocks
         }
         // ---- download on the copy-out stream
         HIPCK(hipStreamWaitEvent(c->s_d2h, S.ev_k, 0));
-        HIPCK(hipMemcpyAsync(S.h_meta, d_len, u32b * 4, hipMemcpyDeviceToHost, c->s_d2h));
-        HIPCK(hipMemcpyAsync(S.h_meta + 4 * (size_t)n, S.status.p, u32b, hipMemcpyDeviceToHost, c->s_d2h));
-        S.b0 = b0; S.n = n;
+        if ((rc = fetch_results(S, b0, n, c->s_d2h)) != ZPQ_OK) return rc;
         if (out_bytes) {
             if (out_dev_view) {
                 // the GPU packs each block's produced bytes straight into the caller's (pinned) slab
                 hipLaunchKernelGGL(k_gather, dim3(n), dim3(256), 0, c->s_d2h, (const uint8_t *)S.out.p, (const uint64_t *)S.outoff.p,
-                                   (const uint32_t *)d_len, out_dev_view, (const uint64_t *)S.dstoff.p, n, skip, 1);
+                                   (const uint32_t *)S.meta.p, out_dev_view, (const uint64_t *)S.dstoff.p, n, skip, 1);
                 HIPCK(hipGetLastError());
             } else {
                 // pageable destination: the runtime stages this copy and the call returns only when it has run, so
@@ -902,8 +971,8 @@ static int host_pipeline(zpq_ctx *c, const zpq_model *m, int decode, int nblocks
     }
     HIPCK(hipStreamSynchronize(c->s_d2h));
     HIPCK(hipStreamSynchronize(c->stream));
-    deliver(c->pipe[nrounds & 1]);                                             // (older round first)
-    deliver(c->pipe[(nrounds + 1) & 1]);
+    deliver(c->pipe[nrounds & 1], h, decode);                                  // (older round first)
+    deliver(c->pipe[(nrounds + 1) & 1], h, decode);
     c->last_host = did | ((unsigned)nrounds << 8);
     return ZPQ_OK;
 }
@@ -912,8 +981,7 @@ extern "C" int zpq_encode_blocks(zpq_ctx *c, const zpq_model *m, int nblocks, co
                                  const uint64_t *in_off, uint32_t flags, uint8_t *out,
                                  const uint64_t *out_off, uint32_t *out_len, int32_t *status) try
 {
-    return host_batch(c, m, 0, nblocks, in, in_off, flags & 0xffu, out, out_off, out_len, nullptr, nullptr,
-                      nullptr, status, nullptr, nullptr, 0, nullptr, 0);
+    return host_batch(c, m, 0, block_arrays(nblocks, in, in_off, flags & 0xffu, out, out_off, out_len, status));
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 extern "C" int zpq_decode_blocks(zpq_ctx *c, const zpq_model *m, int nblocks, const uint8_t *in,
@@ -921,31 +989,27 @@ extern "C" int zpq_decode_blocks(zpq_ctx *c, const zpq_model *m, int nblocks, co
                                  const uint64_t *out_off, uint32_t *out_len, uint32_t *consumed,
                                  uint32_t *final_code, uint32_t *first_byte, int32_t *status) try
 {
-    return host_batch(c, m, 1, nblocks, in, in_off, flags & 0xffu, out, out_off, out_len, consumed,
-                      final_code, first_byte, status, nullptr, nullptr, 0, nullptr, 0);
+    return host_batch(c, m, 1, block_arrays(nblocks, in, in_off, flags & 0xffu, out, out_off, out_len, status, consumed, final_code, first_byte));
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 // ------------------------------------------------------------------ several GPUs behind one call
 // Blocks are independent (compressor.v:90,147-148: fresh Predictor/ZPAQL per block), so any static deal gives the same
 // bytes.  Context g takes the g-th contiguous share -- contiguous so that its PCIe transfers are -- on its own host
 // thread (one host thread per device, no cross-device step but the caller's own buffers).
-static int multi_batch(zpq_ctx *const *ctxs, int nctx, const zpq_model *m, int decode, int nblocks, const uint8_t *in,
-                       const uint64_t *in_off, uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len,
-                       uint32_t *consumed, uint32_t *final_code, uint32_t *first_byte, int32_t *status)
+static int multi_batch(zpq_ctx *const *ctxs, int nctx, const zpq_model *m, int decode, const BlockArrays &h)
 {
+    const int nblocks = h.n;
     if (!ctxs || nctx <= 0 || !m || nblocks < 0) return ZPQ_E_ARG;
     for (int g = 0; g < nctx; g++) if (!ctxs[g]) return ZPQ_E_ARG;
     if (nblocks == 0) return ZPQ_OK;
-    if (!in_off || !out_off || !out_len || !status) return ZPQ_E_ARG;
+    if (!h.in_off || !h.out_off || !h.out_len || !h.status) return ZPQ_E_ARG;
     const int G = nctx < nblocks ? nctx : nblocks;
     std::vector<int> rcs((size_t)G, ZPQ_OK);
     std::vector<std::thread> th;
     for (int g = 0; g < G; g++) {
         const int b0 = (int)((int64_t)nblocks * g / G), b1 = (int)((int64_t)nblocks * (g + 1) / G);
         th.emplace_back([=, &rcs]() {
-            rcs[(size_t)g] = host_batch(ctxs[g], m, decode, b1 - b0, in, in_off + b0, flags, out, out_off + b0, out_len + b0,
-                                        consumed ? consumed + b0 : nullptr, final_code ? final_code + b0 : nullptr,
-                                        first_byte ? first_byte + b0 : nullptr, status + b0, nullptr, nullptr, 0, nullptr, 0);
+            rcs[(size_t)g] = host_batch(ctxs[g], m, decode, h.window(b0, b1));
         });
     }
     for (std::thread &t : th) t.join();
@@ -957,7 +1021,7 @@ extern "C" int zpq_encode_blocks_multi(zpq_ctx *const *ctxs, int nctx, const zpq
                                        const uint64_t *in_off, uint32_t flags, uint8_t *out, const uint64_t *out_off,
                                        uint32_t *out_len, int32_t *status) try
 {
-    return multi_batch(ctxs, nctx, m, 0, nblocks, in, in_off, flags & 0xffu, out, out_off, out_len, nullptr, nullptr, nullptr, status);
+    return multi_batch(ctxs, nctx, m, 0, block_arrays(nblocks, in, in_off, flags & 0xffu, out, out_off, out_len, status));
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 extern "C" int zpq_decode_blocks_multi(zpq_ctx *const *ctxs, int nctx, const zpq_model *m, int nblocks, const uint8_t *in,
@@ -965,7 +1029,7 @@ extern "C" int zpq_decode_blocks_multi(zpq_ctx *const *ctxs, int nctx, const zpq
                                        uint32_t *out_len, uint32_t *consumed, uint32_t *final_code, uint32_t *first_byte,
                                        int32_t *status) try
 {
-    return multi_batch(ctxs, nctx, m, 1, nblocks, in, in_off, flags & 0xffu, out, out_off, out_len, consumed, final_code, first_byte, status);
+    return multi_batch(ctxs, nctx, m, 1, block_arrays(nblocks, in, in_off, flags & 0xffu, out, out_off, out_len, status, consumed, final_code, first_byte));
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 // ------------------------------------------------------------------ slab compaction
@@ -1055,23 +1119,26 @@ extern "C" int zpq_sha1_blocks(zpq_ctx *c, int nblocks, const uint8_t *in, const
     if (nblocks < 0) return ZPQ_E_ARG;
     if (nblocks == 0) return ZPQ_OK;
     if (!in_off || !out20) return ZPQ_E_ARG;
-    for (int b = 0; b < nblocks; b++) if (in_off[b + 1] < in_off[b]) return ZPQ_E_ARG;
-    const size_t base = (size_t)in_off[0], in_bytes = (size_t)in_off[nblocks] - base;
-    if (in_bytes && !in) return ZPQ_E_ARG;
+    BlockArrays h;
+    h.n = nblocks; h.in = in; h.in_off = in_off;
+    if (!slabs_valid(h, false)) return ZPQ_E_ARG;
+    const size_t base = (size_t)in_off[0], in_bytes = (size_t)h.in_bytes();
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCK(hipSetDevice(c->device));
+    // (no results but the digests: the one-shot set lends its in / inoff / out buffers, nothing of stage_upload applies)
+    StageSet &S = c->one;
     int rc;
     const size_t offb = (size_t)(nblocks + 1) * 8;
-    if ((rc = c->s_in.ensure(in_bytes + 16)) || (rc = c->s_inoff.ensure(offb)) || (rc = c->s_out.ensure((size_t)nblocks * 20)))
+    if ((rc = S.in.ensure(in_bytes + 16)) || (rc = S.inoff.ensure(offb)) || (rc = S.out.ensure((size_t)nblocks * 20)))
         return rc;
     std::vector<uint64_t> rel((size_t)nblocks + 1);
     for (int b = 0; b <= nblocks; b++) rel[b] = in_off[b] - base;
     hipStream_t s = c->stream;
-    if (in_bytes) HIPCK(hipMemcpyAsync(c->s_in.p, in + base, in_bytes, hipMemcpyHostToDevice, s));
-    HIPCK(hipMemcpyAsync(c->s_inoff.p, rel.data(), offb, hipMemcpyHostToDevice, s));
-    rc = zpq_launch_sha1((const uint8_t *)c->s_in.p, (const uint64_t *)c->s_inoff.p, (const uint64_t *)c->s_inoff.p + 1, nblocks, (uint8_t *)c->s_out.p, s);
+    if (in_bytes) HIPCK(hipMemcpyAsync(S.in.p, in + base, in_bytes, hipMemcpyHostToDevice, s));
+    HIPCK(hipMemcpyAsync(S.inoff.p, rel.data(), offb, hipMemcpyHostToDevice, s));
+    rc = zpq_launch_sha1((const uint8_t *)S.in.p, (const uint64_t *)S.inoff.p, (const uint64_t *)S.inoff.p + 1, nblocks, (uint8_t *)S.out.p, s);
     if (rc != ZPQ_OK) return rc;
-    HIPCK(hipMemcpyAsync(out20, c->s_out.p, (size_t)nblocks * 20, hipMemcpyDeviceToHost, s));
+    HIPCK(hipMemcpyAsync(out20, S.out.p, (size_t)nblocks * 20, hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
     return ZPQ_OK;
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
@@ -1126,8 +1193,9 @@ static int block_materialise(zpq_block *b)
     uint32_t olen = 0;
     int32_t st = 0;
     uint8_t dummy = 0;
-    const int rc = host_batch(b->ctx, b->model, 0, 1, b->lazy_in.data(), in_off, b->lazy_flags | ZPQ_FLAG_GENERIC, &dummy, out_off, &olen,
-                              nullptr, nullptr, nullptr, &st, b->slot, nullptr, 0, nullptr, 0);
+    BatchExtras x;
+    x.own_slot = b->slot;
+    const int rc = host_batch(b->ctx, b->model, 0, block_arrays(1, b->lazy_in.data(), in_off, b->lazy_flags | ZPQ_FLAG_GENERIC, &dummy, out_off, &olen, &st), x);
     if (rc != ZPQ_OK) return rc;
     if (st != ZPQ_OK && st != ZPQ_E_OVERFLOW) return st;
     b->lazy = false;
@@ -1136,34 +1204,56 @@ static int block_materialise(zpq_block *b)
     return ZPQ_OK;
 }
 
+// One segment of a block, either direction.  `ran`: the call reached the device and r holds what it answered (the caller
+// then fills its out parameters, whatever the status).
+struct SegResult { uint32_t len = 0, consumed = 0, code = 0, first = 0xFFFFFFFFu; bool ran = false; };
+static int block_segment(zpq_block *b, int decode, const uint8_t *in, size_t n, uint32_t flags, uint8_t *out, size_t cap, SegResult *r)
+{
+    if (!b->ctx) return ZPQ_E_CLOSED;                   // the block's ctx has been destroyed
+    const uint64_t in_off[2] = {0, n}, out_off[2] = {0, cap};
+    int32_t st = 0;
+    BlockArrays h = block_arrays(1, in, in_off, flags & 0xffu, out, out_off, &r->len, &st);
+    if (decode) { h.consumed = &r->consumed; h.final_code = &r->code; h.first_byte = &r->first; }
+    if (!(b->fresh && !(flags & ZPQ_FLAG_GENERIC))) {
+        // a later segment (or the generic kernel asked for): on the block's own slot
+        if (int rcm = block_materialise(b)) return rcm;
+        h.flags |= ZPQ_FLAG_GENERIC | (b->fresh ? 0u : ZB_KEEP_STATE);
+        BatchExtras x;
+        x.own_slot = b->slot;
+        const int rc = host_batch(b->ctx, b->model, decode, h, x);
+        if (rc != ZPQ_OK) return rc;
+        r->ran = true;
+        b->fresh = false;
+        return st;
+    }
+    h.flags |= ZB_NO_VMPIPE;
+    const int rc = host_batch(b->ctx, b->model, decode, h);
+    if (rc != ZPQ_OK) return rc;
+    r->ran = true;
+    if (st != ZPQ_OK) return st;                        // nothing persisted: the block is still fresh, the caller may retry
+    b->fresh = false;
+    b->lazy = true;
+    b->lazy_flags = flags & 0xffu;
+    if (!decode) { b->lazy_in.assign(in, in + n); return ZPQ_OK; }
+    // the symbols this segment coded: [PP byte] + output.  With ZPQ_FLAG_PP the first symbol came back in `first`
+    // (0xFFFFFFFF = the stream ended before it); a later encode replays 0 as the PP byte, anything else literally.
+    b->lazy_in.clear();
+    if (flags & ZPQ_FLAG_PP) {
+        if (r->first == 0xFFFFFFFFu) b->lazy_flags &= ~(uint32_t)ZPQ_FLAG_PP;
+        else if (r->first != 0) { b->lazy_flags &= ~(uint32_t)ZPQ_FLAG_PP; b->lazy_in.push_back((uint8_t)r->first); }
+    }
+    b->lazy_in.insert(b->lazy_in.end(), out, out + r->len);
+    return ZPQ_OK;
+}
+
 extern "C" int zpq_block_encode_segment(zpq_block *b, const uint8_t *in, size_t n, uint32_t flags,
                                         uint8_t *out, size_t cap, size_t *out_len) try
 {
     if (!b || !out_len || (n && !in) || (cap && !out)) return ZPQ_E_ARG;
-    if (!b->ctx) return ZPQ_E_CLOSED;                   // the block's ctx has been destroyed
-    const uint64_t in_off[2] = {0, n}, out_off[2] = {0, cap};
-    uint32_t olen = 0;
-    int32_t st = 0;
-    if (b->fresh && !(flags & ZPQ_FLAG_GENERIC)) {
-        int rc = host_batch(b->ctx, b->model, 0, 1, in, in_off, (flags & 0xffu) | ZB_NO_VMPIPE, out, out_off, &olen, nullptr, nullptr,
-                            nullptr, &st, nullptr, nullptr, 0, nullptr, 0);
-        if (rc != ZPQ_OK) return rc;
-        *out_len = olen;
-        if (st != ZPQ_OK) return st;                    // nothing persisted: the block is still fresh, the caller may retry
-        b->fresh = false;
-        b->lazy = true;
-        b->lazy_in.assign(in, in + n);
-        b->lazy_flags = flags & 0xffu;
-        return ZPQ_OK;
-    }
-    if (int rcm = block_materialise(b)) return rcm;
-    const uint32_t f = (flags & 0xffu) | ZPQ_FLAG_GENERIC | (b->fresh ? 0u : ZB_KEEP_STATE);
-    int rc = host_batch(b->ctx, b->model, 0, 1, in, in_off, f, out, out_off, &olen, nullptr, nullptr,
-                        nullptr, &st, b->slot, nullptr, 0, nullptr, 0);
-    if (rc != ZPQ_OK) return rc;
-    b->fresh = false;
-    *out_len = olen;
-    return st;
+    SegResult r;
+    const int rc = block_segment(b, 0, in, n, flags, out, cap, &r);
+    if (r.ran) *out_len = r.len;
+    return rc;
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 extern "C" int zpq_block_decode_segment(zpq_block *b, const uint8_t *in, size_t n, uint32_t flags,
@@ -1171,43 +1261,15 @@ extern "C" int zpq_block_decode_segment(zpq_block *b, const uint8_t *in, size_t 
                                         uint32_t *final_code, uint32_t *first_byte) try
 {
     if (!b || !out_len || (n && !in) || (cap && !out)) return ZPQ_E_ARG;
-    if (!b->ctx) return ZPQ_E_CLOSED;                   // the block's ctx has been destroyed
-    const uint64_t in_off[2] = {0, n}, out_off[2] = {0, cap};
-    uint32_t olen = 0, cons = 0, code = 0, first = 0xFFFFFFFFu;
-    int32_t st = 0;
-    if (b->fresh && !(flags & ZPQ_FLAG_GENERIC)) {
-        int rc = host_batch(b->ctx, b->model, 1, 1, in, in_off, (flags & 0xffu) | ZB_NO_VMPIPE, out, out_off, &olen, &cons, &code, &first,
-                            &st, nullptr, nullptr, 0, nullptr, 0);
-        if (rc != ZPQ_OK) return rc;
-        *out_len = olen;
-        if (consumed) *consumed = cons;
-        if (final_code) *final_code = code;
-        if (first_byte) *first_byte = first;
-        if (st != ZPQ_OK) return st;                    // still fresh
-        // the symbols this segment coded: [PP byte] + output.  With ZPQ_FLAG_PP the first symbol came back in `first`
-        // (0xFFFFFFFF = the stream ended before it); a later encode replays 0 as the PP byte, anything else literally.
-        b->fresh = false;
-        b->lazy = true;
-        b->lazy_in.clear();
-        b->lazy_flags = flags & 0xffu;
-        if (flags & ZPQ_FLAG_PP) {
-            if (first == 0xFFFFFFFFu) b->lazy_flags &= ~(uint32_t)ZPQ_FLAG_PP;
-            else if (first != 0) { b->lazy_flags &= ~(uint32_t)ZPQ_FLAG_PP; b->lazy_in.push_back((uint8_t)first); }
-        }
-        b->lazy_in.insert(b->lazy_in.end(), out, out + olen);
-        return ZPQ_OK;
+    SegResult r;
+    const int rc = block_segment(b, 1, in, n, flags, out, cap, &r);
+    if (r.ran) {
+        *out_len = r.len;
+        if (consumed) *consumed = r.consumed;
+        if (final_code) *final_code = r.code;
+        if (first_byte) *first_byte = r.first;
     }
-    if (int rcm = block_materialise(b)) return rcm;
-    const uint32_t f = (flags & 0xffu) | ZPQ_FLAG_GENERIC | (b->fresh ? 0u : ZB_KEEP_STATE);
-    int rc = host_batch(b->ctx, b->model, 1, 1, in, in_off, f, out, out_off, &olen, &cons, &code, &first,
-                        &st, b->slot, nullptr, 0, nullptr, 0);
-    if (rc != ZPQ_OK) return rc;
-    b->fresh = false;
-    *out_len = olen;
-    if (consumed) *consumed = cons;
-    if (final_code) *final_code = code;
-    if (first_byte) *first_byte = first;
-    return st;
+    return rc;
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 // ------------------------------------------------------------------ N blocks, many segments
@@ -1216,14 +1278,10 @@ extern "C" int zpq_block_decode_segment(zpq_block *b, const uint8_t *in, size_t 
 static bool set_layout(const zpq_ctx *c, const zpq_model *m, uint64_t max_member_bytes, DModel *layout, uint32_t *sp)
 {
     *sp = 0;
-    const bool chain = m->d.fast_kind && zpq_chain_blocks_per_wg(&m->d) > 0;
-    if (!chain) { *layout = m->d; return false; }
-    const char *ev = getenv("ZPQ_SPARSE_FORCE_LOG2");
-    const int lg = ev ? atoi(ev) : 0;
-    const uint32_t cap = (lg >= 8 && lg <= 25) ? (1u << lg) : (max_member_bytes ? line_store_cap(c, max_member_bytes) : c->sparse_cap);
-    const char *mode = getenv("ZPQ_SPARSE_MODE");
-    const bool never = mode && !strcmp(mode, "never");
-    if (!never && zpq_sparse_layout(m->d, cap, layout) && zpq_chain_blocks_per_wg(layout) > 0) *sp = cap;
+    if (!is_chain_model(m)) { *layout = m->d; return false; }
+    const SparseKnobs K = sparse_knobs();
+    const uint32_t cap = K.forced_cap ? K.forced_cap : (max_member_bytes ? line_store_cap(c, max_member_bytes) : c->sparse_cap);
+    if (!K.never && zpq_sparse_layout(m->d, cap, layout) && zpq_chain_blocks_per_wg(layout) > 0) *sp = cap;
     else *layout = m->d;
     return true;
 }
@@ -1231,16 +1289,15 @@ static bool set_layout(const zpq_ctx *c, const zpq_model *m, uint64_t max_member
 // ZPQ_SET_LANES, a request: honoured where no chain kernel takes the model and the lane-per-component kernels do.  The
 // environment variable ZPQ_SET_LANES=1 sets it for every set of the process, ZPQ_SET_LANES=0 clears it (anything but a
 // leading '0' or '1' decides nothing, as with ZPQ_VM_PIPE).  Host logic only: no device is needed.
-static bool set_is_chain(const zpq_model *m) { return m->d.fast_kind && zpq_chain_blocks_per_wg(&m->d) > 0; }
 extern "C" int zpq_blockset_lanes_applies(const zpq_model *m) try
 {
-    return m && !set_is_chain(m) && zpq_lanes_supported(&m->d) ? 1 : 0;
+    return m && !is_chain_model(m) && zpq_lanes_supported(&m->d) ? 1 : 0;
 } ZPQ_CATCH(return 0)
 // ZPQ_SET_PIPE, a request of the same kind: honoured where the wave-pipelined encoder codes the model's chain (its five
 // shapes); ZPQ_SET_PIPE=1 / =0 in the environment by the same rule.  No model can have both.
 extern "C" int zpq_blockset_pipe_applies(const zpq_model *m) try
 {
-    return m && set_is_chain(m) && zpq_pipe_shape_applies(&m->d) ? 1 : 0;
+    return m && is_chain_model(m) && zpq_pipe_shape_applies(&m->d) ? 1 : 0;
 } ZPQ_CATCH(return 0)
 // ZPQ_SET_WAVES, a request on top of ZPQ_SET_LANES: honoured where that one is in force for the set and both wave-per-component
 // kernels take the model (gpipe_cfg: the shape alone; ZPQ_ENC_GPIPE / ZPQ_DEC_GPIPE choose the kernel per call, not here).
@@ -1257,19 +1314,13 @@ extern "C" int zpq_blockset_vmwaves_applies(const zpq_model *m) try
 {
     return zpq_blockset_lanes_applies(m) && zpq_vpipe_applies(&m->d) ? 1 : 0;
 } ZPQ_CATCH(return 0)
-static bool set_request(const char *var, uint32_t flags, uint32_t bit)
-{
-    const char *ev = getenv(var);
-    const bool env = ev && (ev[0] == '0' || ev[0] == '1');
-    return env ? ev[0] == '1' : (flags & bit) != 0;
-}
 extern "C" int zpq_blockset_resolve_flags(const zpq_model *m, uint32_t flags) try
 {
     if (!m || (flags & ~(uint32_t)ZPQ_SET_ALL)) return ZPQ_E_ARG;
-    const bool lanes = set_request("ZPQ_SET_LANES", flags, ZPQ_SET_LANES) && zpq_blockset_lanes_applies(m);
-    const bool pipe = set_request("ZPQ_SET_PIPE", flags, ZPQ_SET_PIPE) && zpq_blockset_pipe_applies(m);
-    const bool waves = lanes && set_request("ZPQ_SET_WAVES", flags, ZPQ_SET_WAVES) && zpq_blockset_waves_applies(m);
-    const bool vmwaves = lanes && set_request("ZPQ_SET_VMWAVES", flags, ZPQ_SET_VMWAVES) && zpq_blockset_vmwaves_applies(m);
+    const bool lanes = request("ZPQ_SET_LANES", flags, ZPQ_SET_LANES) && zpq_blockset_lanes_applies(m);
+    const bool pipe = request("ZPQ_SET_PIPE", flags, ZPQ_SET_PIPE) && zpq_blockset_pipe_applies(m);
+    const bool waves = lanes && request("ZPQ_SET_WAVES", flags, ZPQ_SET_WAVES) && zpq_blockset_waves_applies(m);
+    const bool vmwaves = lanes && request("ZPQ_SET_VMWAVES", flags, ZPQ_SET_VMWAVES) && zpq_blockset_vmwaves_applies(m);
     return (int)((lanes ? ZPQ_SET_LANES : 0u) | (pipe ? ZPQ_SET_PIPE : 0u) | (waves ? ZPQ_SET_WAVES : 0u) | (vmwaves ? ZPQ_SET_VMWAVES : 0u));
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
@@ -1291,7 +1342,7 @@ extern "C" int zpq_blockset_capacity_ex(zpq_ctx *c, const zpq_model *m, uint64_t
     if (!m) return ZPQ_E_ARG;
     HIPCK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mu);
-    static thread_local DModel layout;
+    DModel layout;
     uint32_t sp = 0;
     const bool chain = set_layout(c, m, max_member_bytes, &layout, &sp);
     // (ZPQ_SET_PIPE changes nothing here: any round of such a set may fall back to the chain encoder; nor do ZPQ_SET_WAVES / _VMWAVES:
@@ -1385,22 +1436,17 @@ extern "C" void zpq_blockset_destroy(zpq_blockset *s) try
     delete s;
 } ZPQ_CATCH(return)
 
-static int set_segments(zpq_blockset *s, int decode, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
-                        uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, uint32_t *consumed,
-                        uint32_t *final_code, uint32_t *first_byte, int32_t *status)
+static int set_segments(zpq_blockset *s, int decode, const int32_t *member, const BlockArrays &h)
 {
+    const int n = h.n;
     if (!s) return ZPQ_E_ARG;
     zpq_ctx *c = s->ctx;
     if (!c) return ZPQ_E_CLOSED;
     if (!ctx_live(c)) return ZPQ_E_CLOSED;
-    if (n < 0 || n > s->nmembers || (flags & ZPQ_FLAG_NOEOF)) return ZPQ_E_ARG;
+    if (n < 0 || n > s->nmembers || (h.flags & ZPQ_FLAG_NOEOF)) return ZPQ_E_ARG;
     if (n == 0) return ZPQ_OK;
-    if (!in_off || !out_off || !out_len || !status) return ZPQ_E_ARG;
-    for (int b = 0; b < n; b++)
-        if (in_off[b + 1] < in_off[b] || out_off[b + 1] < out_off[b] ||
-            in_off[b + 1] - in_off[b] > 0xFFFFFFF0ull || out_off[b + 1] - out_off[b] > 0xFFFFFFF0ull)
-            return ZPQ_E_ARG;
-    if ((in_off[n] > in_off[0] && !in) || (out_off[n] > out_off[0] && !out)) return ZPQ_E_ARG;
+    if (!h.in_off || !h.out_off || !h.out_len || !h.status) return ZPQ_E_ARG;
+    if (!slabs_valid(h)) return ZPQ_E_ARG;
     std::vector<int32_t> mem((size_t)n);
     {
         std::vector<uint8_t> seen((size_t)s->nmembers, 0);
@@ -1415,135 +1461,105 @@ static int set_segments(zpq_blockset *s, int decode, int n, const int32_t *membe
     HIPCK(hipSetDevice(c->device));
     // failed members report their status and take no part; the rest are packed into one batch
     std::vector<int> live;
+    uint64_t in_bytes = 0, out_bytes = 0;
     for (int i = 0; i < n; i++) {
         const int32_t f = s->failed[(size_t)mem[(size_t)i]];
         if (f != ZPQ_OK) {
-            status[i] = f; out_len[i] = 0;
-            if (consumed) consumed[i] = 0;
-            if (final_code) final_code[i] = 0;
-            if (first_byte) first_byte[i] = 0xFFFFFFFFu;
-        } else live.push_back(i);
+            h.status[i] = f; h.out_len[i] = 0;
+            if (h.consumed) h.consumed[i] = 0;
+            if (h.final_code) h.final_code[i] = 0;
+            if (h.first_byte) h.first_byte[i] = 0xFFFFFFFFu;
+        } else {
+            live.push_back(i);
+            in_bytes += h.in_off[i + 1] - h.in_off[i];
+            out_bytes += h.out_off[i + 1] - h.out_off[i];
+        }
     }
     const int k = (int)live.size();
     if (k == 0) return ZPQ_OK;
     const bool all = k == n;
-    std::vector<uint64_t> h_in((size_t)k + 1), h_out((size_t)k + 1);
+    StageSet &S = c->one;
+    hipStream_t st = c->stream;
+    const size_t u32b = (size_t)k * 4;
+    int rc = stage_room(S, k, (size_t)in_bytes, (size_t)out_bytes, u32b + 16);
+    if (rc != ZPQ_OK) return rc;
+    // the live members' slabs one behind the other (with all of them live that is the caller's window as it stands)
+    uint64_t *const h_in = S.h_in(), *const h_out = S.h_out(k);
     std::vector<int32_t> h_map((size_t)k);
     h_in[0] = 0; h_out[0] = 0;
     for (int j = 0; j < k; j++) {
         const int i = live[(size_t)j];
         // (16-byte aligned slabs: the kernels read and write them by dwords)
-        h_in[(size_t)j + 1] = all ? in_off[i + 1] - in_off[0] : h_in[(size_t)j] + (in_off[i + 1] - in_off[i]);
-        h_out[(size_t)j + 1] = all ? out_off[i + 1] - out_off[0] : h_out[(size_t)j] + (out_off[i + 1] - out_off[i]);
+        h_in[j + 1] = h_in[j] + (h.in_off[i + 1] - h.in_off[i]);
+        h_out[j + 1] = h_out[j] + (h.out_off[i + 1] - h.out_off[i]);
         h_map[(size_t)j] = mem[(size_t)i];
     }
-    const size_t in_bytes = (size_t)h_in[(size_t)k], out_bytes = (size_t)h_out[(size_t)k];
-    const size_t offb = (size_t)(k + 1) * 8, u32b = (size_t)k * 4;
-    int rc;
-    if ((rc = c->s_in.ensure(in_bytes + 16)) || (rc = c->s_out.ensure(out_bytes + 16)) || (rc = c->s_inoff.ensure(offb)) ||
-        (rc = c->s_outoff.ensure(offb)) || (rc = c->s_status.ensure(u32b)) || (rc = c->s_misc.ensure(u32b + 16)))
-        return rc;
-    for (auto &b : c->s_u32) if ((rc = b.ensure(u32b))) return rc;
-    hipStream_t st = c->stream;
-    if (all) { if (in_bytes) HIPCK(hipMemcpyAsync(c->s_in.p, in + in_off[0], in_bytes, hipMemcpyHostToDevice, st)); }
+    if (all) { if (in_bytes) HIPCK(hipMemcpyAsync(S.in.p, h.in + h.in_off[0], (size_t)in_bytes, hipMemcpyHostToDevice, st)); }
     else for (int j = 0; j < k; j++) {
         const int i = live[(size_t)j];
-        const size_t len = (size_t)(in_off[i + 1] - in_off[i]);
-        if (len) HIPCK(hipMemcpyAsync((uint8_t *)c->s_in.p + h_in[(size_t)j], in + in_off[i], len, hipMemcpyHostToDevice, st));
+        const size_t len = (size_t)(h.in_off[i + 1] - h.in_off[i]);
+        if (len) HIPCK(hipMemcpyAsync((uint8_t *)S.in.p + h_in[j], h.in + h.in_off[i], len, hipMemcpyHostToDevice, st));
     }
-    HIPCK(hipMemcpyAsync(c->s_inoff.p, h_in.data(), offb, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(c->s_outoff.p, h_out.data(), offb, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(c->s_misc.p, h_map.data(), u32b, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemsetAsync(c->s_status.p, 0xff, u32b, st));   // -1: "kernel never reported"
-    HIPCK(hipMemsetAsync(c->s_u32[0].p, 0, u32b, st));
-    uint32_t *d_len = (uint32_t *)c->s_u32[0].p, *d_cons = (uint32_t *)c->s_u32[1].p, *d_code = (uint32_t *)c->s_u32[2].p,
-             *d_first = (uint32_t *)c->s_u32[3].p;
+    HIPCK(hipMemcpyAsync(S.misc.p, h_map.data(), u32b, hipMemcpyHostToDevice, st));
+    if ((rc = stage_upload(S, k, st, false)) != ZPQ_OK) return rc;
+    BlockArrays dv = S.device_view(k, h.flags & 0xffu, decode);
     if (s->chain || (s->flags & ZPQ_SET_LANES)) {
         DevModel dm;
         if ((rc = get_dev_model(c, s->model, s->layout, s->sp, &dm)) != ZPQ_OK) return rc;
-        DBatch B;
-        memset(&B, 0, sizeof B);
-        B.model = dm.d_model; B.img = dm.d_img;
-        B.slots = s->slots; B.nslots = k; B.nblocks = k;
-        B.flags = (flags & 0xffu & ~(uint32_t)(ZPQ_FLAG_GENERIC | ZPQ_FLAG_LANES)) | ZB_KEEP_STATE;
-        B.in = (const uint8_t *)c->s_in.p; B.in_off = (const uint64_t *)c->s_inoff.p;
-        B.out = (uint8_t *)c->s_out.p; B.out_off = (const uint64_t *)c->s_outoff.p;
-        B.out_len = d_len; B.status = (int32_t *)c->s_status.p;
-        if (decode) { B.consumed = d_cons; B.final_code = d_code; B.first_byte = d_first; }
-        B.squash = c->d_squash; B.stretch = c->d_stretch; B.dt = c->d_dt; B.dt2k = c->d_dt2k;
-        B.ns = c->d_ns; B.stretch_c = c->d_stretch_c;
-        B.slot_map = (const int32_t *)c->s_misc.p;
-        if (!decode && (s->flags & ZPQ_SET_PIPE)) B.flags |= ZB_SET_PIPE;   // this call may run on k_pipe<..., KEEP> (zpq_launch_chain)
+        dv.flags = (dv.flags & ~(uint32_t)(ZPQ_FLAG_GENERIC | ZPQ_FLAG_LANES)) | ZB_KEEP_STATE;
+        if (!decode && (s->flags & ZPQ_SET_PIPE)) dv.flags |= ZB_SET_PIPE;   // this call may run on k_pipe<..., KEEP> (zpq_launch_chain)
+        DBatch B = batch_base(c, dm, dv);
+        B.slots = s->slots; B.nslots = k;
+        B.slot_map = (const int32_t *)S.misc.p;
         c->last_slots = k;
         c->last_sp = s->sp;
         if (s->chain) {
-            int bpw = 0;
-            if (!zpq_chain_plan(&s->layout, k, c->cus, &bpw)) return ZPQ_E_INTERNAL;
-            const int grid = (k + bpw - 1) / bpw;
-            if (grid > zpq_chain_max_wgs(&s->layout, c->cus)) return ZPQ_E_INTERNAL;   // (nmembers <= capacity rules this out)
-            HIPCK(hipEventRecord(c->ev0, st));
-            const char *name = nullptr;
-            if ((rc = zpq_launch_chain(&B, &s->layout, decode, grid, bpw, st, &name)) != ZPQ_OK) return rc;
-            c->last_name = name;
+            Plan P;
+            P.fam = F_CHAIN; P.sp = s->sp; P.M = s->layout; P.nslots = k;
+            if (!zpq_chain_plan(&s->layout, k, c->cus, &P.bpw)) return ZPQ_E_INTERNAL;
+            P.grid = (k + P.bpw - 1) / P.bpw;
+            if (P.grid > zpq_chain_max_wgs(&s->layout, c->cus)) return ZPQ_E_INTERNAL;   // (nmembers <= capacity rules this out)
+            if ((rc = launch_family(c, B, P, decode, st)) != ZPQ_OK) return rc;
         } else {
             // the round in one launch of k_rows / k_lanes<..., KEEP>: any number of members, no workgroup waits for another
             // ZPQ_SET_WAVES: this call runs on k_wset / k_wsetd unless ZPQ_ENC_GPIPE=0 / ZPQ_DEC_GPIPE=0 says otherwise right now;
             // the slot format is one, so calls on a set may alternate.  No floor on k.  ZPQ_SET_VMWAVES: the same with k_vset / k_vsetd.
+            // (the KEEP launchers are not a batch call's families: they have no row in FAMILY)
             const char *ev = getenv(decode ? "ZPQ_DEC_GPIPE" : "ZPQ_ENC_GPIPE");
             const bool on = !(ev && atoi(ev) == 0);
             const bool waves = (s->flags & ZPQ_SET_WAVES) != 0 && on, vmwaves = (s->flags & ZPQ_SET_VMWAVES) != 0 && on;
-            HIPCK(hipEventRecord(c->ev0, st));
-            if (waves || vmwaves) {
-                const char *name = nullptr;
-                if ((rc = (waves ? zpq_launch_wset : zpq_launch_vset)(&B, &s->layout, decode, st, &name)) != ZPQ_OK) return rc;
-                c->last_name = name;
-            } else {
-                if ((rc = zpq_launch_lanes_keep(&B, &s->layout, decode, st)) != ZPQ_OK) return rc;
-                c->last_name = zpq_lanes_kernel_name(&s->layout, decode);
-            }
+            rc = timed_launch(c, st, [&](const char **name) {
+                if (waves || vmwaves) return (waves ? zpq_launch_wset : zpq_launch_vset)(&B, &s->layout, decode, st, name);
+                *name = zpq_lanes_kernel_name(&s->layout, decode);
+                return zpq_launch_lanes_keep(&B, &s->layout, decode, st);
+            });
+            if (rc != ZPQ_OK) return rc;
         }
-        HIPCK(hipGetLastError());
-        HIPCK(hipEventRecord(c->ev1, st));
-        c->ev_valid = true;
     } else {
         // other models: the lane-0 kernel on the member's slot, one launch each (ZB_KEEP_STATE from the second segment on)
         for (int j = 0; j < k; j++) {
             const int32_t mb = h_map[(size_t)j];
             BatchArgs a;
-            memset(&a, 0, sizeof a);
-            a.nblocks = 1; a.in = (const uint8_t *)c->s_in.p; a.in_off = (const uint64_t *)c->s_inoff.p + j;
-            a.flags = (flags & 0xffu) | ZPQ_FLAG_GENERIC | (s->fresh[(size_t)mb] ? 0u : ZB_KEEP_STATE);
-            a.out = (uint8_t *)c->s_out.p; a.out_off = (const uint64_t *)c->s_outoff.p + j; a.out_len = d_len + j;
-            if (decode) { a.consumed = d_cons + j; a.final_code = d_code + j; a.first_byte = d_first + j; }
-            a.status = (int32_t *)c->s_status.p + j;
-            a.own_slot = s->slots + (uint64_t)mb * s->layout.slot_bytes;
+            a.io = dv.window(j, j + 1);
+            a.io.flags = dv.flags | ZPQ_FLAG_GENERIC | (s->fresh[(size_t)mb] ? 0u : ZB_KEEP_STATE);
+            a.x.own_slot = s->slots + (uint64_t)mb * s->layout.slot_bytes;
             if ((rc = run_batch(c, s->model, decode, a)) != ZPQ_OK) { (void)hipStreamSynchronize(st); return rc; }
         }
     }
-    std::vector<uint32_t> r_len((size_t)k), r_cons((size_t)k), r_code((size_t)k), r_first((size_t)k);
-    std::vector<int32_t> r_st((size_t)k);
-    HIPCK(hipMemcpyAsync(r_len.data(), d_len, u32b, hipMemcpyDeviceToHost, st));
-    HIPCK(hipMemcpyAsync(r_st.data(), c->s_status.p, u32b, hipMemcpyDeviceToHost, st));
-    if (decode) {
-        HIPCK(hipMemcpyAsync(r_cons.data(), d_cons, u32b, hipMemcpyDeviceToHost, st));
-        HIPCK(hipMemcpyAsync(r_code.data(), d_code, u32b, hipMemcpyDeviceToHost, st));
-        HIPCK(hipMemcpyAsync(r_first.data(), d_first, u32b, hipMemcpyDeviceToHost, st));
-    }
-    if (all && out_bytes) HIPCK(hipMemcpyAsync(out + out_off[0], c->s_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    if ((rc = fetch_results(S, 0, k, st)) != ZPQ_OK) return rc;
+    if (all && out_bytes) HIPCK(hipMemcpyAsync(h.out + h.out_off[0], S.out.p, (size_t)out_bytes, hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
+    deliver(S, h, decode, live.data());
     for (int j = 0; j < k; j++) {
         const int i = live[(size_t)j];
         const int32_t mb = h_map[(size_t)j];
-        out_len[i] = r_len[(size_t)j]; status[i] = r_st[(size_t)j];
-        if (decode && consumed) consumed[i] = r_cons[(size_t)j];
-        if (decode && final_code) final_code[i] = r_code[(size_t)j];
-        if (decode && first_byte) first_byte[i] = r_first[(size_t)j];
         s->fresh[(size_t)mb] = 0;
-        if (r_st[(size_t)j] != ZPQ_OK) s->failed[(size_t)mb] = r_st[(size_t)j];
+        if (h.status[i] != ZPQ_OK) s->failed[(size_t)mb] = h.status[i];
         if (!all) {
-            const uint64_t cap = out_off[i + 1] - out_off[i];
-            const size_t got = (size_t)(r_len[(size_t)j] < cap ? r_len[(size_t)j] : cap);
-            if (got) HIPCK(hipMemcpyAsync(out + out_off[i], (uint8_t *)c->s_out.p + h_out[(size_t)j], got, hipMemcpyDeviceToHost, st));
+            // a set with failed members: each live member's slab on its own, only what was produced
+            const uint64_t cap = h.out_off[i + 1] - h.out_off[i];
+            const size_t got = (size_t)(h.out_len[i] < cap ? h.out_len[i] : cap);
+            if (got) HIPCK(hipMemcpyAsync(h.out + h.out_off[i], (uint8_t *)S.out.p + h_out[j], got, hipMemcpyDeviceToHost, st));
         }
     }
     if (!all) HIPCK(hipStreamSynchronize(st));
@@ -1553,14 +1569,14 @@ static int set_segments(zpq_blockset *s, int decode, int n, const int32_t *membe
 extern "C" int zpq_blockset_encode_segments(zpq_blockset *s, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
                                             uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status) try
 {
-    return set_segments(s, 0, n, member, in, in_off, flags, out, out_off, out_len, nullptr, nullptr, nullptr, status);
+    return set_segments(s, 0, member, block_arrays(n, in, in_off, flags, out, out_off, out_len, status));
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 extern "C" int zpq_blockset_decode_segments(zpq_blockset *s, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
                                             uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, uint32_t *consumed,
                                             uint32_t *final_code, uint32_t *first_byte, int32_t *status) try
 {
-    return set_segments(s, 1, n, member, in, in_off, flags, out, out_off, out_len, consumed, final_code, first_byte, status);
+    return set_segments(s, 1, member, block_arrays(n, in, in_off, flags, out, out_off, out_len, status, consumed, final_code, first_byte));
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 // ------------------------------------------------------------------ test hooks
@@ -1572,8 +1588,9 @@ extern "C" int zpq_debug_contexts(zpq_ctx *c, const zpq_model *m, const uint8_t 
     uint32_t olen = 0;
     int32_t st = 0;
     uint8_t dummy = 0;
-    int rc = host_batch(c, m, 0, 1, in, in_off, ZPQ_FLAG_GENERIC | ZB_CTX_ONLY, &dummy, out_off, &olen,
-                        nullptr, nullptr, nullptr, &st, nullptr, nullptr, 0, h_out, n * (size_t)m->d.n);
+    BatchExtras x;
+    x.ctx_out = h_out; x.ctx_words = n * (size_t)m->d.n;
+    int rc = host_batch(c, m, 0, block_arrays(1, in, in_off, ZPQ_FLAG_GENERIC | ZB_CTX_ONLY, &dummy, out_off, &olen, &st), x);
     return rc != ZPQ_OK ? rc : st;
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
@@ -1585,8 +1602,9 @@ extern "C" int zpq_debug_encode_trace(zpq_ctx *c, const zpq_model *m, const uint
     const uint64_t in_off[2] = {0, n}, out_off[2] = {0, cap};
     uint32_t olen = 0;
     int32_t st = 0;
-    int rc = host_batch(c, m, 0, 1, in, in_off, (flags & 0xffu) | ZPQ_FLAG_GENERIC, out, out_off, &olen,
-                        nullptr, nullptr, nullptr, &st, nullptr, p_trace, (uint32_t)ntrace, nullptr, 0);
+    BatchExtras x;
+    x.trace = p_trace; x.ntrace = (uint32_t)ntrace;
+    int rc = host_batch(c, m, 0, block_arrays(1, in, in_off, (flags & 0xffu) | ZPQ_FLAG_GENERIC, out, out_off, &olen, &st), x);
     if (rc != ZPQ_OK) return rc;
     *out_len = olen;
     return st;

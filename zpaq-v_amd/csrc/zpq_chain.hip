@@ -1644,14 +1644,8 @@ extern "C" int zpq_chain_has_hio(const DModel *M)
     return build_cfg(M, &cfg) && !cfg.sparse && (cfg.nch_spec == 2 || cfg.nch_spec == 3) ? 1 : 0;
 }
 
-// zpq_pipe.hip: the wave-pipelined encoder of the chains without a MIX2
-extern "C" int zpq_pipe_applies(const DModel *M, int blocks_per_wg, int nslots);
-extern "C" int zpq_launch_pipe(const DBatch *B, const DModel *hostM, int nwg, int blocks_per_wg, hipStream_t stream, const char **name_out);
-
-// zpq_dpipe.hip: the wave-split decoder of the dense chains without a MIX2
-extern "C" int zpq_dpipe_applies(const DModel *M, int blocks_per_wg, int nslots);
-extern "C" int zpq_launch_dpipe(const DBatch *B, const DModel *hostM, int nwg, int blocks_per_wg, hipStream_t stream);
-
+// (zpq_pipe.hip: the wave-pipelined encoder of the chains without a MIX2; zpq_dpipe.hip: the wave-split decoder of the
+// dense chains without a MIX2 -- both declared in zpq_host.h)
 extern "C" int zpq_launch_chain(const DBatch *B, const DModel *hostM, int decode, int nwg, int blocks_per_wg,
                                 hipStream_t stream, const char **name_out)
 {

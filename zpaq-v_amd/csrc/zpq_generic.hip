@@ -23,6 +23,7 @@
 #include "zpq_common.h"
 #include "zpq_vm.h"
 #include "zpq_dev.h"
+#include "zpq_host.h"
 
 namespace zpqg {
 

@@ -28,6 +28,7 @@
 #include "zpq_common.h"
 #include "zpq_chain_cfg.h"
 #include "zpq_dev.h"
+#include "zpq_host.h"
 
 namespace zpqp {
 

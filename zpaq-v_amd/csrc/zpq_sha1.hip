@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/zpaq_hip.h"
+#include "zpq_host.h"
 
 namespace zpqs {
 
