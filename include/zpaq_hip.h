@@ -372,6 +372,49 @@ int zpq_blockset_encode_segments(zpq_blockset *, int n, const int32_t *member, c
 int zpq_blockset_decode_segments(zpq_blockset *, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
                                  uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, uint32_t *consumed,
                                  uint32_t *final_code, uint32_t *first_byte, int32_t *status);
+/*
+ * CHUNKED coding: a member's segment a piece at a time -- what Compressor.compress(n) (compressor.v:259-293) and
+ * Decompresser.decompress(n) (decompressor.v:443-515) do n bytes at a time, the coder and the predictor carrying on between
+ * calls.  A member is OPEN after a chunk call that left its segment unfinished; the set remembers it
+ * (zpq_blockset_member_open: 1 / 0, < 0 = ZPQ_E_*), and the next chunk call on that member goes on where the last one
+ * stopped -- no new coder, no Predictor.reset(), no PP byte, whatever `flags` says.  One call may mix members that start,
+ * go on and end.  Arguments, windows (above, "The window contract") and the copy-back of slabs ("The rest of a slab") are
+ * those of zpq_blockset_{encode,decode}_segments.
+ *   encode   member i not open: a segment starts as in zpq_blockset_encode_segments (new coder, reset(), the PP byte under
+ *            ZPQ_FLAG_PP).  more[i] != 0: the call stops behind the last input byte -- no compress(-1), no flush() --, stores
+ *            what the Encoder has put() so far and leaves the member open; more[i] == 0 (more == NULL: all 0) ends the
+ *            segment.  Zero input bytes are legal both to open a segment (the PP byte is then all that is coded) and to end
+ *            one.  The bytes of a segment's chunks, one behind the other, are exactly what ONE zpq_blockset_encode_segments
+ *            call writes for the whole segment; with more == NULL and no member open the call IS that call.  A slab too small
+ *            for its chunk fails the member (ZPQ_E_OVERFLOW, sticky), as do ZPQ_E_TOOBIG / ZPQ_E_VMSTEPS: max_member_bytes
+ *            covers all chunks of all segments.
+ *   decode   a decoder PAUSES instead of overflowing: once it has stored cap = out_off[i+1] - out_off[i] bytes it stops in
+ *            front of the next byte's EOF flag -- nothing more is decoded, the model is not touched -- and reports out_len[i]
+ *            = cap, open[i] = 1, status[i] = ZPQ_OK, consumed[i] and final_code[i] as of that point.  (A segment that starts
+ *            under ZPQ_FLAG_PP decodes the PP byte first and reports it in first_byte[i]; a call that goes on reports
+ *            0xFFFFFFFF.)  The next call reads on from where the decoder stands: its window starts consumed[i] bytes behind
+ *            the previous window's start; consumed[] counts per call.  Reaching the EOF symbol closes the member, open[i] = 0;
+ *            a stream that ends exactly with a full slab takes one more call (out_len 0, open 0) to find that out, and so cap
+ *            = 0 decodes nothing.  ZPQ_E_OVERFLOW is never reported.  open[] (n entries) is required.  A window that ends
+ *            before the chunk's data does reads zeros past its end, as in zpq_decode_blocks: enough input for the bytes a
+ *            call is to decode is the CALLER'S duty (a decoder runs four bytes, its code register, ahead of the bits it has
+ *            decoded; passing the whole rest of the stream is the simple choice).
+ * An open member listed in zpq_blockset_{encode,decode}_segments, or in a chunk call of the other direction, makes the call
+ * return ZPQ_E_ARG with nothing coded; ZPQ_FLAG_NOEOF stays ZPQ_E_ARG; a failed member is never open.
+ * Kernels: chain models on k_chain<..., KEEP> in both directions -- on a ZPQ_SET_PIPE set too, every encode_chunks call runs on
+ * "k_chain<encode>" (same slot format, as for that flag's per-call choice) --, every other model on the lane-0 kernel, a launch
+ * per member.  A set on which ZPQ_SET_LANES is in force (flags 1, 17, 65) returns ZPQ_E_ARG from both chunk calls: carrying
+ * the pause to k_rows / k_lanes / k_wset / k_vset is later work, as are zpq_block_* and the archive layer / front end (which
+ * still re-decode with a larger slab).
+ */
+int zpq_blockset_encode_chunks(zpq_blockset *, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
+                               uint32_t flags, const uint8_t *more /* n entries, NULL = all 0 */,
+                               uint8_t *out, const uint64_t *out_off, uint32_t *out_len, int32_t *status);
+int zpq_blockset_decode_chunks(zpq_blockset *, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
+                               uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len,
+                               uint32_t *consumed, uint32_t *final_code, uint32_t *first_byte,
+                               uint8_t *open /* n entries, out, required */, int32_t *status);
+int zpq_blockset_member_open(const zpq_blockset *, int member);   /* 1 = its segment is open, 0 = not, < 0 = ZPQ_E_* */
 
 /* ---- inspection / test hooks ---- */
 /* squash_table / stretch_table as built at start-up (predictor.v:11-15,21-96). */

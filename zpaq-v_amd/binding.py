@@ -133,6 +133,10 @@ def lib():
     L.zpq_blockset_resolve_flags.argtypes = [vp, u32]
     L.zpq_blockset_encode_segments.argtypes = [vp, i32, vp, vp, vp, u32, vp, vp, vp, vp]
     L.zpq_blockset_decode_segments.argtypes = [vp, i32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "zpq_blockset_encode_chunks"):           # (a ZPQ_LIB_PATH build from before chunked coding lacks the three)
+        L.zpq_blockset_encode_chunks.argtypes = [vp, i32, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+        L.zpq_blockset_decode_chunks.argtypes = [vp, i32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.zpq_blockset_member_open.argtypes = [vp, i32]
     L.zpq_tables.argtypes = [vp, vp]
     L.zpq_tables_ex.argtypes = [vp, vp, vp]
     L.zpq_debug_contexts.argtypes = [vp, vp, u8p, C.c_size_t, vp]
@@ -596,3 +600,77 @@ class BlockSet:
             "zpq_blockset_decode_segments")
         res = [out[int(out_off[i]):int(out_off[i]) + min(int(out_len[i]), cap)].tobytes() for i in range(n)]
         return res, status, consumed, code, first
+
+    def member_open(self, m):
+        """Is member m's segment open, i.e. did a chunk call leave it unfinished (zpq_blockset_member_open)?"""
+        rc = lib().zpq_blockset_member_open(self.h, m)
+        if rc < 0:
+            raise ZpqError(rc, "zpq_blockset_member_open")
+        return bool(rc)
+
+    def encode_chunks(self, chunks, more, members=None, flags=FLAG_PP, cap=None):
+        """zpq_blockset_encode_chunks: the next piece of each listed member's segment; more[i] true = the segment goes on
+        after it (None = every chunk ends its segment).  A segment's pieces joined are what encode_segments gives for the
+        whole of it.  Returns (coded, status, out_len)."""
+        n = len(chunks)
+        keep, mp = self._members(members, n)
+        in_off = _offsets([len(b) for b in chunks])
+        src = np.frombuffer(b"".join(chunks) + b"\0", dtype=np.uint8)
+        if isinstance(cap, (list, tuple)):                 # one output capacity per chunk
+            caps = [int(x) for x in cap]
+        else:
+            caps = [cap if cap is not None else len(b) * 17 + 4096 for b in chunks]
+        out_off = _offsets(caps)
+        out = np.zeros(int(out_off[-1]) + 1, dtype=np.uint8)
+        out_len = np.zeros(n, dtype=np.uint32)
+        status = np.zeros(n, dtype=np.int32)
+        mo = None if more is None else np.asarray([1 if x else 0 for x in more], dtype=np.uint8)
+        assert mo is None or len(mo) == n
+        _ck(lib().zpq_blockset_encode_chunks(self.h, n, mp, src.ctypes.data, in_off.ctypes.data, flags,
+                                             None if mo is None else mo.ctypes.data, out.ctypes.data, out_off.ctypes.data,
+                                             out_len.ctypes.data, status.ctypes.data),
+            "zpq_blockset_encode_chunks")
+        res = [out[int(out_off[i]):int(out_off[i]) + min(int(out_len[i]), caps[i])].tobytes() for i in range(n)]
+        return res, status, out_len
+
+    def decode_chunks(self, coded, cap, members=None, flags=FLAG_PP):
+        """zpq_blockset_decode_chunks: up to cap (one number, or one per member) more bytes of each listed member's segment
+        from coded[i], the coded bytes from where the member's decoder stands on.  A decoder whose slab is full pauses
+        (open[i] = 1) instead of overflowing.  Returns (bytes, status, consumed, final_code, first_byte, open)."""
+        n = len(coded)
+        keep, mp = self._members(members, n)
+        in_off = _offsets([len(b) for b in coded])
+        src = np.frombuffer(b"".join(coded) + b"\0", dtype=np.uint8)
+        caps = [int(x) for x in cap] if isinstance(cap, (list, tuple)) else [int(cap)] * n
+        out_off = _offsets(caps)
+        out = np.zeros(int(out_off[-1]) + 1, dtype=np.uint8)
+        out_len = np.zeros(n, dtype=np.uint32)
+        consumed = np.zeros(n, dtype=np.uint32)
+        code = np.zeros(n, dtype=np.uint32)
+        first = np.zeros(n, dtype=np.uint32)
+        opened = np.zeros(n, dtype=np.uint8)
+        status = np.zeros(n, dtype=np.int32)
+        _ck(lib().zpq_blockset_decode_chunks(self.h, n, mp, src.ctypes.data, in_off.ctypes.data, flags, out.ctypes.data,
+                                             out_off.ctypes.data, out_len.ctypes.data, consumed.ctypes.data,
+                                             code.ctypes.data, first.ctypes.data, opened.ctypes.data, status.ctypes.data),
+            "zpq_blockset_decode_chunks")
+        res = [out[int(out_off[i]):int(out_off[i]) + min(int(out_len[i]), caps[i])].tobytes() for i in range(n)]
+        return res, status, consumed, code, first, opened
+
+    def encode_chunks_raw(self, members, in_ptr, in_off, flags, more, out_ptr, out_off):
+        """zpq_blockset_encode_chunks on caller buffers and offsets (any window).  Returns (rc, out_len, status)."""
+        n = len(in_off) - 1
+        keep, mp = self._members(members, n)
+        mo = None if more is None else np.asarray([1 if x else 0 for x in more], dtype=np.uint8)
+        fn = lib().zpq_blockset_encode_chunks
+        return _enc_raw(lambda *a: fn(*a[:6], None if mo is None else mo.ctypes.data, *a[6:]), (self.h, n, mp), n, in_ptr,
+                        in_off, flags, out_ptr, out_off)
+
+    def decode_chunks_raw(self, members, in_ptr, in_off, flags, out_ptr, out_off):
+        """zpq_blockset_decode_chunks likewise.  Returns (rc, out_len, consumed, final_code, first_byte, status, open)."""
+        n = len(in_off) - 1
+        keep, mp = self._members(members, n)
+        opened = np.full(n, 0xEE, dtype=np.uint8)
+        fn = lib().zpq_blockset_decode_chunks
+        return _dec_raw(lambda *a: fn(*a[:-1], opened.ctypes.data, a[-1]), (self.h, n, mp), n, in_ptr, in_off, flags,
+                        out_ptr, out_off) + (opened,)

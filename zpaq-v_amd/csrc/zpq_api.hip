@@ -270,6 +270,7 @@ struct zpq_blockset {
     uint64_t bytes = 0;
     std::vector<int32_t> failed;   // per member: ZPQ_OK, or the status its first failing segment ended with (sticky)
     std::vector<uint8_t> fresh;    // per member: no segment coded yet (the generic route initialises in-kernel)
+    std::vector<uint8_t> open;     // per member: a chunk call left its segment unfinished (1 = the encoder did, 2 = the decoder; 0 = no)
 };
 
 // ------------------------------------------------------------------ ctx
@@ -1392,6 +1393,7 @@ extern "C" int zpq_blockset_create_ex(zpq_ctx *c, const zpq_model *m, int nmembe
     if (rc != ZPQ_OK) { (void)hipGetLastError(); (void)hipFree(s->slots); delete s; return rc; }
     s->failed.assign((size_t)nmembers, ZPQ_OK);
     s->fresh.assign((size_t)nmembers, 1);
+    s->open.assign((size_t)nmembers, 0);
     s->ctx = c; s->model = m;
     {
         std::lock_guard<std::mutex> lk2(g_reg_mu);
@@ -1436,7 +1438,11 @@ extern "C" void zpq_blockset_destroy(zpq_blockset *s) try
     delete s;
 } ZPQ_CATCH(return)
 
-static int set_segments(zpq_blockset *s, int decode, const int32_t *member, const BlockArrays &h)
+// chunk = a zpq_blockset_*_chunks call: members may stop in the middle of their segment (encode: more[i] != 0, NULL = none;
+// decode: the slab is full) and are then OPEN, which the set remembers and reports in open_out[]; an open member goes on
+// from there in the next chunk call.  Without chunk an open member is refused.
+static int set_segments(zpq_blockset *s, int decode, const int32_t *member, const BlockArrays &h, bool chunk = false,
+                        const uint8_t *more = nullptr, uint8_t *open_out = nullptr)
 {
     const int n = h.n;
     if (!s) return ZPQ_E_ARG;
@@ -1457,7 +1463,13 @@ static int set_segments(zpq_blockset *s, int decode, const int32_t *member, cons
             mem[(size_t)i] = k;
         }
     }
+    if (chunk && ((s->flags & ZPQ_SET_LANES) || s->layout.n < 1 || (decode && !open_out))) return ZPQ_E_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
+    // an open segment belongs to the chunk calls of the direction that opened it
+    for (int i = 0; i < n; i++) {
+        const uint8_t o = s->open[(size_t)mem[(size_t)i]];
+        if (o && (!chunk || o != (decode ? 2 : 1))) return ZPQ_E_ARG;
+    }
     HIPCK(hipSetDevice(c->device));
     // failed members report their status and take no part; the rest are packed into one batch
     std::vector<int> live;
@@ -1469,6 +1481,7 @@ static int set_segments(zpq_blockset *s, int decode, const int32_t *member, cons
             if (h.consumed) h.consumed[i] = 0;
             if (h.final_code) h.final_code[i] = 0;
             if (h.first_byte) h.first_byte[i] = 0xFFFFFFFFu;
+            if (open_out) open_out[i] = 0;
         } else {
             live.push_back(i);
             in_bytes += h.in_off[i + 1] - h.in_off[i];
@@ -1493,6 +1506,8 @@ static int set_segments(zpq_blockset *s, int decode, const int32_t *member, cons
         h_in[j + 1] = h_in[j] + (h.in_off[i + 1] - h.in_off[i]);
         h_out[j + 1] = h_out[j] + (h.out_off[i + 1] - h.out_off[i]);
         h_map[(size_t)j] = mem[(size_t)i];
+        if (chunk && s->chain)   // (k_chain<..., KEEP> alone reads these marks: chunk calls never run on k_pipe)
+            h_map[(size_t)j] |= (s->open[(size_t)mem[(size_t)i]] ? ZB_MAP_CONT : 0) | (!decode && more && more[i] ? ZB_MAP_MORE : 0);
     }
     if (all) { if (in_bytes) HIPCK(hipMemcpyAsync(S.in.p, h.in + h.in_off[0], (size_t)in_bytes, hipMemcpyHostToDevice, st)); }
     else for (int j = 0; j < k; j++) {
@@ -1507,7 +1522,8 @@ static int set_segments(zpq_blockset *s, int decode, const int32_t *member, cons
         DevModel dm;
         if ((rc = get_dev_model(c, s->model, s->layout, s->sp, &dm)) != ZPQ_OK) return rc;
         dv.flags = (dv.flags & ~(uint32_t)(ZPQ_FLAG_GENERIC | ZPQ_FLAG_LANES)) | ZB_KEEP_STATE;
-        if (!decode && (s->flags & ZPQ_SET_PIPE)) dv.flags |= ZB_SET_PIPE;   // this call may run on k_pipe<..., KEEP> (zpq_launch_chain)
+        if (chunk) dv.flags |= ZB_CHUNK;                                            // (always k_chain<..., KEEP>, ZPQ_SET_PIPE or not)
+        else if (!decode && (s->flags & ZPQ_SET_PIPE)) dv.flags |= ZB_SET_PIPE;   // this call may run on k_pipe<..., KEEP> (zpq_launch_chain)
         DBatch B = batch_base(c, dm, dv);
         B.slots = s->slots; B.nslots = k;
         B.slot_map = (const int32_t *)S.misc.p;
@@ -1542,6 +1558,10 @@ static int set_segments(zpq_blockset *s, int decode, const int32_t *member, cons
             BatchArgs a;
             a.io = dv.window(j, j + 1);
             a.io.flags = dv.flags | ZPQ_FLAG_GENERIC | (s->fresh[(size_t)mb] ? 0u : ZB_KEEP_STATE);
+            if (chunk) {
+                const int i = live[(size_t)j];
+                a.io.flags |= ZB_CHUNK | (s->open[(size_t)mb] ? ZB_CHUNK_CONT : 0u) | (!decode && more && more[i] ? ZB_CHUNK_MORE : 0u);
+            }
             a.x.own_slot = s->slots + (uint64_t)mb * s->layout.slot_bytes;
             if ((rc = run_batch(c, s->model, decode, a)) != ZPQ_OK) { (void)hipStreamSynchronize(st); return rc; }
         }
@@ -1552,9 +1572,16 @@ static int set_segments(zpq_blockset *s, int decode, const int32_t *member, cons
     deliver(S, h, decode, live.data());
     for (int j = 0; j < k; j++) {
         const int i = live[(size_t)j];
-        const int32_t mb = h_map[(size_t)j];
+        const int32_t mb = h_map[(size_t)j] & ZB_MAP_SLOT;              // (a chunk call on a chain set: the entry carries ZB_MAP_* as well)
         s->fresh[(size_t)mb] = 0;
+        // still open: an encoder that was told so; a decoder that says it paused, its slab full, in front of the next EOF flag
+        // (ZB_ST_PAUSED, which stays in here).  A failed member is never open.
+        const bool paused = chunk && decode && h.status[i] == ZB_ST_PAUSED;
+        if (paused) h.status[i] = ZPQ_OK;
         if (h.status[i] != ZPQ_OK) s->failed[(size_t)mb] = h.status[i];
+        const bool op = chunk && h.status[i] == ZPQ_OK && (decode ? paused : (more && more[i]));
+        s->open[(size_t)mb] = op ? (decode ? 2 : 1) : 0;
+        if (open_out) open_out[i] = op ? 1 : 0;
         if (!all) {
             // a set with failed members: each live member's slab on its own, only what was produced
             const uint64_t cap = h.out_off[i + 1] - h.out_off[i];
@@ -1577,6 +1604,31 @@ extern "C" int zpq_blockset_decode_segments(zpq_blockset *s, int n, const int32_
                                             uint32_t *final_code, uint32_t *first_byte, int32_t *status) try
 {
     return set_segments(s, 1, member, block_arrays(n, in, in_off, flags, out, out_off, out_len, status, consumed, final_code, first_byte));
+} ZPQ_CATCH(return ZPQ_E_INTERNAL)
+
+extern "C" int zpq_blockset_encode_chunks(zpq_blockset *s, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
+                                          uint32_t flags, const uint8_t *more, uint8_t *out, const uint64_t *out_off,
+                                          uint32_t *out_len, int32_t *status) try
+{
+    return set_segments(s, 0, member, block_arrays(n, in, in_off, flags, out, out_off, out_len, status), true, more);
+} ZPQ_CATCH(return ZPQ_E_INTERNAL)
+
+extern "C" int zpq_blockset_decode_chunks(zpq_blockset *s, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
+                                          uint32_t flags, uint8_t *out, const uint64_t *out_off, uint32_t *out_len, uint32_t *consumed,
+                                          uint32_t *final_code, uint32_t *first_byte, uint8_t *open, int32_t *status) try
+{
+    return set_segments(s, 1, member, block_arrays(n, in, in_off, flags, out, out_off, out_len, status, consumed, final_code, first_byte),
+                        true, nullptr, open);
+} ZPQ_CATCH(return ZPQ_E_INTERNAL)
+
+extern "C" int zpq_blockset_member_open(const zpq_blockset *s, int member) try
+{
+    if (!s) return ZPQ_E_ARG;
+    zpq_ctx *c = s->ctx;
+    if (!c || !ctx_live(c)) return ZPQ_E_CLOSED;
+    if (member < 0 || member >= s->nmembers) return ZPQ_E_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return s->open[(size_t)member] ? 1 : 0;
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 // ------------------------------------------------------------------ test hooks

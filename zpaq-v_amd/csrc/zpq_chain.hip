@@ -115,6 +115,14 @@ struct BitCtx {
 // (DVmRegs: the interpreter's registers, or prev / m4, b4 in its pad words), the line store's claim count and full flag
 // (DCompScal a / b of the component, which only a MATCH uses otherwise).  Block i works on slot slot_map[i], one block per
 // slot and launch.  The byte loop is the same code: everything KEEP adds sits in front of it and behind it.
+// KEEP also carries a member across a launch boundary in the MIDDLE of a segment (zpq_blockset_*_chunks: compress(n) /
+// decompress(n), compressor.v:259-293, decompressor.v:443-515).  A pause is always at the top of a byte iteration (c8 == 1, slot
+// == 1, the context program run), so what it adds to the saved state is the coder's registers (DCompScal c / limit / cxt of the
+// last component, which only a MATCH uses otherwise) and every lane's h[] (hctx, in its component's pad_[1]: reset() zeroes
+// h[] but not H, so it cannot be reloaded from z.h).  Which members go on (ZB_MAP_CONT: no new coder, no reset(), no PP byte)
+// and which stay open (ZB_MAP_MORE: no compress(-1) / flush()) is per member, in the spare high bits of the slot_map entries;
+// under ZB_CHUNK a decoder whose slab is full leaves the byte loop behind the byte that filled it, in front of the next EOF
+// flag (the overflow exit, one byte earlier), and reports ZB_ST_PAUSED.
 template <bool DEC, bool SPEC, int NCH, bool MIXT, int GG, bool SP, bool HIO = false, bool KEEP = false>
 __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg cfg)
 {
@@ -176,11 +184,17 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
     const int slot_id = blockIdx.x * cfg.blocks_per_wg + bslot;
     const int nslots = B.nslots;                       // may be less than gridDim.x * blocks_per_wg
     u8 *slot = B.slots + (u64)slot_id * M.slot_bytes;
+    int map_e = 0;                                     // KEEP: the block's slot_map entry, slot index | ZB_MAP_*
     if constexpr (KEEP) {
         // (groups beyond the batch code nothing; they only must not read past the map)
         const int si = slot_id < nslots ? slot_id : 0;
-        slot = B.slots + (u64)(B.slot_map ? B.slot_map[si] : si) * M.slot_bytes;
+        map_e = B.slot_map ? B.slot_map[si] : si;
+        slot = B.slots + (u64)(map_e & ZB_MAP_SLOT) * M.slot_bytes;
     }
+    const bool cont = KEEP && (map_e & ZB_MAP_CONT) != 0;   // the member's segment is open: go on where it stopped
+    const bool more = KEEP && (map_e & ZB_MAP_MORE) != 0;   // encode: the segment stays open behind this launch
+    // the PP byte opens a segment, not a chunk (the other instantiations read the flag where they always did)
+#define ZPQ_IS_PP (KEEP ? (u32)((B.flags & ZPQ_FLAG_PP) && !cont) : (B.flags & ZPQ_FLAG_PP))
     u8 *my = lds + L_STATE + bslot * cfg.lds_per_block;
 
     const int n = NCH ? NCH + (MIXT ? 1 : 0) : cfg.n;
@@ -331,6 +345,14 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             z.a = kregs->a; z.b = kregs->b; z.c = kregs->c; z.d = kregs->d; z.f = kregs->f; z.pc = kregs->pc;
             prev = kregs->pad_[0]; m4 = kregs->pad_[0]; b4 = kregs->pad_[1];
         }
+        u32 k_low = 1, k_high = 0xFFFFFFFFu, k_code = 0;   // the coder as a pause left it
+        if constexpr (KEEP) {
+            if (cont) {
+                const DCompScal *const ks = reinterpret_cast<const DCompScal *>(slot + M.scal_off) + (lc < n ? lc : 0);
+                hctx = ks->pad_[1];
+                if (is_last) { k_low = (u32)ks->c; k_high = (u32)ks->limit; k_code = ks->cxt; }
+            }
+        }
 
         // Input window: the next bytes of `src` live in two registers, refilled by aligned
         // dword loads issued a whole dword ahead of use (never a load on the bit path).
@@ -396,13 +418,18 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
         X.r0 = X.r1 = X.r2 = X.r3 = 0; X.slot = 1; X.c8 = 1;
         u32 first = 0xFFFFFFFFu;
         bool got_first = false;
+        if constexpr (KEEP) { X.low = k_low; X.high = k_high; X.code = k_code; }
         if (DEC) {
             dec_request(0u);
             dec_adopt();
             dec_request(0u);                               // (adopted by the first byte iteration)
+            if constexpr (KEEP) {
+                if (!cont) for (int k = 0; k < 4; k++) { const u32 c = in_byte(X.ipos); X.ipos += (X.ipos < nin); X.code = (X.code << 8) | c; }
+            } else {
             for (int k = 0; k < 4; k++) { const u32 c = in_byte(X.ipos); X.ipos += (X.ipos < nin); X.code = (X.code << 8) | c; }
+            }
         }
-        const u32 total = DEC ? 0xFFFFFFFFu : nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u);
+        const u32 total = DEC ? 0xFFFFFFFFu : nin + (ZPQ_IS_PP ? 1u : 0u);
         u32 ch = 0;
         u32 roff = 0;                                      // tbase offset of the row in X.r0..r3
 
@@ -1283,8 +1310,16 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
 
         // nibble start: find_ht (predictor.v:495-532); three rows of one 64-byte line
 
+        if constexpr (KEEP) {
+            // (h = 0 unless the segment goes on: then what the last byte before the pause left, the MIX2's from its lane)
+            prefetch_rows(hctx, 1u);
+            const u32 hm = (u32)row_bcast((i32)hctx, row_base + comp_lane(last));
+            if (MIXS) hctx_mix = hm;
+            if (DEC && mixreg) { if (MIXS) mixs_request(hm, 1u); else mixw_request(hm, 1u); }
+        } else {
         prefetch_rows(0u, 1u);                             // first nibble of the first byte: h = 0, c8 = 1
         if (DEC && mixreg) { if (MIXS) mixs_request(0u, 1u); else mixw_request(0u, 1u); }
+        }
         // Encode, specialised kernels: the prediction chain as a PIPELINE over bytes.  Every context, bit and
         // bit-history state of the encoder is a function of the input alone; only predictions flow down the chain.
         // So in iteration `it` lane c works on byte it - c: the ICM is one byte ahead of the first ISSE, which is one
@@ -1295,7 +1330,11 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
         bool pend_store = false;                           // decode: the last decoded byte still has to be stored
         u32 pend_pos = 0, pend_val = 0;
         const u32 skew_delay = SKEW ? (u32)li : 0u;
-        const u32 iters = SKEW ? total + (u32)last : total;
+        u32 iters = SKEW ? total + (u32)last : total;
+        if constexpr (KEEP && DEC) {
+            // chunk call with a slab of no bytes: nothing is decoded but the PP byte that opens a segment
+            if ((B.flags & ZB_CHUNK) && cap == 0u) iters = ZPQ_IS_PP ? 1u : 0u;
+        }
         // HIO: the byte loop runs in two phases with the host hand-shake between them (wave-uniform iteration counts: the
         // encoder's lanes are at most 15 bytes apart, every decoder iteration after the PP byte stores one byte)
         const u32 split = !HIO ? iters
@@ -1312,9 +1351,9 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             if (!SKEW || bi < total) {
             if (DEC) { dec_adopt(); dec_request(X.ipos); }
             if (!DEC) {
-                const u32 cpos = (B.flags & ZPQ_FLAG_PP) ? bi - 1u : bi;
-                const u32 cb = enc_byte((B.flags & ZPQ_FLAG_PP) && bi == 0 ? 0u : cpos);
-                ch = ((B.flags & ZPQ_FLAG_PP) && bi == 0) ? 0u : cb;
+                const u32 cpos = ZPQ_IS_PP ? bi - 1u : bi;
+                const u32 cb = enc_byte(ZPQ_IS_PP && bi == 0 ? 0u : cpos);
+                ch = (ZPQ_IS_PP && bi == 0) ? 0u : cb;
             }
             // ---- EOF flag: encode(0,0) / decode(0)  (encoder.v:108, decoder.v:128)
             if (!DEC) {
@@ -1378,7 +1417,7 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             if (MIXS) hctx_mix = hnext_mix;
 
             if (DEC) {
-                if ((B.flags & ZPQ_FLAG_PP) && !got_first) { first = byte; got_first = true; }
+                if (ZPQ_IS_PP && !got_first) { first = byte; got_first = true; }
                 else {
                     // The byte is STORED behind the next iteration's wait for its rows: a store issued here would be
                     // the youngest memory operation when that wait comes, and vmcnt retires in order.
@@ -1386,6 +1425,11 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
                     pend_pos = X.opos;
                     pend_val = byte;
                     X.opos++;                                 // uniform across the group when decoding
+                    if constexpr (KEEP) {
+                        // chunk call: the slab is full -- pause here, in front of the next byte's EOF flag, instead of decoding one
+                        // byte too many (uniform over the block's lanes like the exit below: all of them count X.opos and share cap)
+                        if (X.opos + ((B.flags & ZB_CHUNK) ? 1u : 0u) > cap) { stop = true; break; }
+                    } else
                     if (X.opos > cap) { stop = true; break; }
                 }
             }
@@ -1471,9 +1515,13 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             if constexpr (SP) {
                 if (wr_lane) { kscal->a = (i32)sp_claims; kscal->b = sp_full ? 1 : 0; }
             }
+            // ... and what a segment that is still open goes on from (see KEEP above): h[] of every component, the coder
+            if (lc < n && hyp == 0) kscal->pad_[1] = hctx;
+            if (!DEC && is_last && more) oq_flush();
+            if (is_last && hyp == 0) { kscal->c = (i32)X.low; kscal->limit = (i32)X.high; kscal->cxt = X.code; }
         }
         // ---- segment end: compress(-1) + flush (encoder.v:101-105,130-139)
-        if (!DEC && is_last) {
+        if (!DEC && is_last && !more) {
             X.high = X.low;                                   // encode(1, 0): mid = low, high = mid
             while ((X.high ^ X.low) < 0x1000000u) {
                 put_byte(X.high >> 24);
@@ -1487,6 +1535,10 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
         if (is_last && hyp == 0) {
             i32 st = st0;
             if (X.opos > cap && st == ZPQ_OK) st = ZPQ_E_OVERFLOW;
+            if constexpr (KEEP && DEC) {
+                // paused (not at the EOF symbol: that exit leaves X.opos < cap, or the PP byte undecoded): the segment stays open
+                if ((B.flags & ZB_CHUNK) && X.opos >= cap && (!ZPQ_IS_PP || got_first) && st == ZPQ_OK) st = ZB_ST_PAUSED;
+            }
             B.out_len[blk] = X.opos;
             B.status[blk] = st;
             if (DEC) {
@@ -1498,6 +1550,7 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
     }
 }
 
+#undef ZPQ_IS_PP
 }  // namespace zpqc
 
 // ------------------------------------------------------------------ host side

@@ -105,3 +105,15 @@ struct DBatch {
 #define ZB_CTX_ONLY 0x200u       // debug: run only the ZPAQL VM and dump contexts
 #define ZB_NO_VMPIPE 0x400u      // zpq_block: neither ZPQ_FLAG_VMPIPE nor ZPQ_VM_PIPE applies
 #define ZB_SET_PIPE 0x800u       // a block set's encode call (with ZB_KEEP_STATE) may run on k_pipe<..., KEEP> (ZPQ_SET_PIPE)
+// Chunk calls on a block set (zpq_blockset_{encode,decode}_chunks): a launch may stop in the middle of a segment and the next
+// one go on from there (compressor.v:259-293, decompressor.v:443-515).
+#define ZB_CHUNK 0x1000u         // a chunk call: a decoder whose slab is full pauses in front of the next byte's EOF flag instead
+                                 // of overflowing; on k_chain<..., KEEP> the slot_map entries carry ZB_MAP_CONT / ZB_MAP_MORE
+#define ZB_CHUNK_CONT 0x2000u    // k_generic (a launch per member): the member's segment is open, go on where it stopped
+#define ZB_CHUNK_MORE 0x4000u    // k_generic, encode: stop after the last input byte, no compress(-1) / flush(): the segment stays open
+// per member in one launch of k_chain<..., KEEP>: the same two marks in the spare high bits of its slot_map entry
+#define ZB_MAP_CONT 0x40000000
+#define ZB_MAP_MORE 0x20000000
+#define ZB_MAP_SLOT 0x0FFFFFFF
+// status[] of a decoder that paused under ZB_CHUNK (kernel to host only: the host reports ZPQ_OK and the member as open)
+#define ZB_ST_PAUSED 1

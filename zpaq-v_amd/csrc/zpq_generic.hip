@@ -450,9 +450,17 @@ __global__ void __launch_bounds__(64) k_generic(const DBatch B)
         if (!(B.flags & ZB_KEEP_STATE)) init_slot(B, slot, lane);
         DCompScal *gs = reinterpret_cast<DCompScal *>(slot + M.scal_off);
         DVmRegs *gr = reinterpret_cast<DVmRegs *>(slot + M.regs_off);
+        // Chunk calls on a block set (zpq_blockset_*_chunks): ZB_CHUNK_CONT = the member's segment is open, this launch goes on
+        // where the last one stopped at a byte boundary (c8 == hmap4 == 1, the ZPAQL program run): no new coder, no reset(), no
+        // PP byte.  What a pause keeps on top of ZB_KEEP_STATE: h[] in DCompScal::pad_[1] (NOT z.h: reset() zeroes h[] and leaves
+        // H alone, so a segment that has coded no byte yet goes on with h[] = 0), the coder's low / high in DVmRegs::pad_[0..1]
+        // (which only the chain kernels use otherwise, on their own sets) and the decoder's code in component 0's pad_[2].
+        const bool cont = (B.flags & ZB_CHUNK_CONT) != 0;
+        const bool pp = (B.flags & ZPQ_FLAG_PP) && !cont;
+        u32 k_low = 1, k_high = 0xFFFFFFFFu, k_code = 0;    // the coder's registers where this launch leaves them (lane 0)
         for (int i = lane; i < M.n; i += 64) {
             S.cs[i] = gs[i];
-            S.h[i] = 0;                              // Predictor.reset() (predictor.v:827-833)
+            S.h[i] = cont ? gs[i].pad_[1] : 0;       // Predictor.reset() (predictor.v:827-833)
             S.p[i] = (B.flags & ZB_KEEP_STATE) ? (i32)gs[i].pad_[0] : 0;   // (reset() leaves p[] alone: below)
             S.row[i] = 0;
             S.cxt[i] = 0;
@@ -495,11 +503,12 @@ __global__ void __launch_bounds__(64) k_generic(const DBatch B)
             }
         } else if (!DEC) {
             Enc e; e.low = 1; e.high = 0xFFFFFFFFu; e.out = dst; e.cap = cap; e.pos = 0;
-            const u32 total = nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u);
+            if (cont) { e.low = gr->pad_[0]; e.high = gr->pad_[1]; }
+            const u32 total = nin + (pp ? 1u : 0u);
             u32 tpos = 0;
             for (u32 i = 0; i < total; i++) {
                 i32 ch = 0;
-                if (B.flags & ZPQ_FLAG_PP) ch = (i == 0) ? 0 : src[i - 1];
+                if (pp) ch = (i == 0) ? 0 : src[i - 1];
                 else ch = src[i];
                 if (lane == 0) enc_bit(e, 0, 0);                // EOF flag, p=0 (encoder.v:108)
                 for (int bit = 7; bit >= 0; bit--) {
@@ -514,7 +523,8 @@ __global__ void __launch_bounds__(64) k_generic(const DBatch B)
                 }
             }
             if (lane == 0) {
-                if (!(B.flags & ZPQ_FLAG_NOEOF)) {
+                k_low = e.low; k_high = e.high;                 // (ZB_CHUNK_MORE: the segment stays open, compress(n) returns here)
+                if (!(B.flags & (ZPQ_FLAG_NOEOF | ZB_CHUNK_MORE))) {
                     enc_bit(e, 1, 0);                           // compress(-1) (encoder.v:101-105)
                     for (int s = 24; s >= 0; s -= 8) {          // flush() (encoder.v:130-139)
                         if (e.pos < e.cap) e.out[e.pos] = (u8)(e.high >> s);
@@ -527,14 +537,18 @@ __global__ void __launch_bounds__(64) k_generic(const DBatch B)
             }
         } else {
             Dec d; d.low = 1; d.high = 0xFFFFFFFFu; d.code = 0; d.in = src; d.n = nin; d.pos = 0;
-            if (lane == 0) for (int i = 0; i < 4; i++) dec_shift(d);    // decoder.v:38-46
+            if (cont) { d.low = gr->pad_[0]; d.high = gr->pad_[1]; d.code = gs[0].pad_[2]; }
+            else if (lane == 0) for (int i = 0; i < 4; i++) dec_shift(d);    // decoder.v:38-46
             u32 opos = 0, first = 0xFFFFFFFFu;
-            bool got_first = false;
+            bool got_first = false, eof_seen = false;
             for (;;) {
+                // a chunk call PAUSES with its slab full, before the next byte's EOF flag (decompress(n) returns, decompressor.v:443-515);
+                // the PP byte of a segment's first call is decoded first
+                if ((B.flags & ZB_CHUNK) && opos >= cap && (!pp || got_first)) break;
                 i32 eof = 0;
                 if (lane == 0) eof = dec_bit(d, 0);                     // decoder.v:128
                 eof = __shfl(eof, 0);
-                if (eof) break;
+                if (eof) { eof_seen = true; break; }
                 u32 c = 1;
                 for (int bit = 0; bit < 8; bit++) {
                     const i32 p = predict(P, lane);
@@ -545,7 +559,7 @@ __global__ void __launch_bounds__(64) k_generic(const DBatch B)
                     if (lane == 0 && !advance(P, z, y)) st = ZPQ_E_VMSTEPS;
                     c = (c << 1) | (u32)y;
                 }
-                if ((B.flags & ZPQ_FLAG_PP) && !got_first) { first = c - 256; got_first = true; }
+                if (pp && !got_first) { first = c - 256; got_first = true; }
                 else {
                     if (opos < cap) { if (lane == 0) dst[opos] = (u8)(c - 256); }
                     opos++;
@@ -553,7 +567,9 @@ __global__ void __launch_bounds__(64) k_generic(const DBatch B)
                 }
             }
             if (lane == 0) {
+                k_low = d.low; k_high = d.high; k_code = d.code;
                 if (opos > cap && st == ZPQ_OK) st = ZPQ_E_OVERFLOW;
+                if ((B.flags & ZB_CHUNK) && !eof_seen && st == ZPQ_OK) st = ZB_ST_PAUSED;   // (the host: ZPQ_OK, the member open)
                 B.out_len[blk] = opos;
                 if (B.consumed) B.consumed[blk] = d.pos;
                 if (B.final_code) B.final_code[blk] = d.code;
@@ -563,9 +579,14 @@ __global__ void __launch_bounds__(64) k_generic(const DBatch B)
         }
         __syncthreads();
         // persist what outlives a segment
-        if (lane == 0) { gr->a = z.a; gr->b = z.b; gr->c = z.c; gr->d = z.d; gr->f = z.f; gr->pc = z.pc; }
+        if (lane == 0) {
+            gr->a = z.a; gr->b = z.b; gr->c = z.c; gr->d = z.d; gr->f = z.f; gr->pc = z.pc;
+            gr->pad_[0] = k_low; gr->pad_[1] = k_high;
+            if (M.n > 0) S.cs[0].pad_[2] = k_code;
+        }
         for (int i = lane; i < M.n; i += 64) {
             S.cs[i].pad_[0] = (u32)S.p[i];
+            S.cs[i].pad_[1] = S.h[i];
             gs[i] = S.cs[i];
         }
         __syncthreads();
