@@ -67,6 +67,31 @@ extern "C" {
                                  block set is the set's own flag, ZPQ_SET_VMWAVES (below).  The environment decides first:
                                  ZPQ_VM_PIPE=1 sets it for every call, ZPQ_VM_PIPE=0 clears it (a value that starts
                                  with neither digit decides nothing). */
+#define ZPQ_FLAG_LINESTORE 32u /* a request: code a general model on k_rows / k_lanes with every ICM / ISSE table that is
+                                 larger than the compact line store (68 bytes per line of zpq_ctx_set_max_block_bytes'
+                                 capacity) kept on such a store instead of a dense table, as the chain kernels keep
+                                 the tables of levels 3-5.  A slot then holds a few MiB where the dense one holds up to
+                                 1 GiB per table: more resident blocks, nothing but the tags to clear per block, and
+                                 batches that otherwise end in ZPQ_E_NOMEM.  Honoured when the call reaches the
+                                 lane-per-component kernels (no chain kernel takes it, or ZPQ_FLAG_LANES; neither
+                                 ZPQ_FLAG_GENERIC nor ZPQ_FLAG_NOEOF; at most 64 components), ZPQ_SPARSE_MODE is not
+                                 "never" and zpq_lanes_store_applies(model, capacity) holds; otherwise the call runs
+                                 exactly as without it.  A honoured request runs k_rows / k_lanes also where the wave
+                                 pipelines (k_gpipe / k_gdec, k_vpipe / k_vdec) would apply: those have no store.  The
+                                 coded bytes are the same either way; the kernel names stay "k_rows<...>" /
+                                 "k_lanes<...>" and zpq_ctx_last_line_store reports the capacity (0 = dense).  A block
+                                 that touches more than 15/16 of the capacity in lines of one table -- larger than
+                                 zpq_ctx_set_max_block_bytes promised -- ends with ZPQ_E_TOOBIG in status[] (behind
+                                 ZPQ_E_VMSTEPS, ahead of ZPQ_E_OVERFLOW), its output unspecified, other blocks
+                                 untouched.  All batch entry points honour it and zpq_ctx_resident_capacity follows it;
+                                 zpq_block_* and zpq_blockset_* ignore the flag and the variable.  The environment
+                                 decides first: ZPQ_LANES_STORE=1 / =0 by the rule of ZPQ_VM_PIPE.  Measured (MI355X,
+                                 C4b with ICM and ISSE at 22 bits, 64 KiB blocks, EXPERIMENTS.md R20): it pays from the
+                                 batch size at which the dense slots no longer hold the batch in one round -- 487
+                                 blocks of that model's 513 MiB slot --: 3.1x / 5.8x (encode / decode) at 2048 blocks,
+                                 9.1x / 16.5x at 8192; at 256 blocks, one round either way, it loses 1.47x on encode
+                                 against k_gpipe and gains 1.24x on decode against k_gdec (against dense k_rows: 8 % and
+                                 3 % slower, the probe).  It stays a request. */
 
 /* ---- header helpers: levels.v:26-375 (get_compression_level) and the scan
  *      that defines cend/hbegin/hend, compressor.v:96-145 ---- */
@@ -82,6 +107,14 @@ void zpq_model_destroy(zpq_model *);
 int zpq_model_ncomp(const zpq_model *);
 uint64_t zpq_model_state_bytes(const zpq_model *); /* device bytes of one block's tables */
 int zpq_model_has_fast_path(const zpq_model *);    /* 1 if the LDS-resident chain kernel applies */
+/* ZPQ_FLAG_LINESTORE's envelope, host logic only (no device): would the request be honoured for this model on a line
+ * store of cap_lines lines (what zpq_ctx_set_max_block_bytes derives from the block size), from the model's shape alone?
+ * 1 when the lane-per-component kernels take the model (1-64 components), cap_lines is a multiple of 4 and at least 16,
+ * at least one ICM / ISSE table is larger than the store (68 * cap_lines bytes) and the slot on the store is below 4 GiB;
+ * else 0.  zpq_lanes_store_slot_bytes: the size of one block's slot under the store (compare zpq_model_state_bytes, the
+ * dense slot), 0 where the store does not apply. */
+int zpq_lanes_store_applies(const zpq_model *, uint32_t cap_lines);
+uint64_t zpq_lanes_store_slot_bytes(const zpq_model *, uint32_t cap_lines);
 
 /* ---- per-device context: stream, read-only tables, per-block state slots ---- */
 /* Handle lifetime: handles may be destroyed in ANY order (a garbage-collected host language will).  zpq_ctx_destroy

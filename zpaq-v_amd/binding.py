@@ -16,6 +16,7 @@ FLAG_PP = 1
 FLAG_GENERIC = 2
 FLAG_LANES = 8
 FLAG_VMPIPE = 16
+FLAG_LINESTORE = 32                          # a request: k_rows / k_lanes with the large ICM / ISSE tables on the compact line store
 SET_LANES = 1                                # zpq_blockset_create_ex / zpq_blockset_capacity_ex
 SET_PIPE = 4
 SET_WAVES = 16
@@ -126,6 +127,9 @@ def lib():
     L.zpq_blockset_capacity_ex.argtypes = [vp, vp, u64, u32]
     L.zpq_blockset_flags.argtypes = [vp]
     L.zpq_blockset_flags.restype = u32
+    L.zpq_lanes_store_applies.argtypes = [vp, u32]
+    L.zpq_lanes_store_slot_bytes.argtypes = [vp, u32]
+    L.zpq_lanes_store_slot_bytes.restype = u64
     L.zpq_blockset_lanes_applies.argtypes = [vp]
     L.zpq_blockset_pipe_applies.argtypes = [vp]
     L.zpq_blockset_waves_applies.argtypes = [vp]
@@ -215,6 +219,14 @@ class Model:
     @property
     def has_fast_path(self):
         return bool(lib().zpq_model_has_fast_path(self.h))
+
+    def lanes_store_applies(self, cap_lines):
+        """Would FLAG_LINESTORE be honoured for this model on a line store of cap_lines lines (host logic, no device)?"""
+        return bool(lib().zpq_lanes_store_applies(self.h, cap_lines))
+
+    def lanes_store_slot_bytes(self, cap_lines):
+        """Bytes of one block's slot under FLAG_LINESTORE at that capacity, 0 where the store does not apply."""
+        return lib().zpq_lanes_store_slot_bytes(self.h, cap_lines)
 
 
 class PinnedArray:

@@ -473,6 +473,24 @@ static SparseKnobs sparse_knobs()
     k.always = k.forced_cap || (mode && !strcmp(mode, "always"));
     return k;
 }
+// ZPQ_FLAG_LINESTORE / ZPQ_LANES_STORE, a request: k_rows / k_lanes with the model's large hashed tables on the compact line
+// store.  The layout it would run on at `cap` lines, from the model's shape alone: the lane kernels take the model, at least
+// one ICM / ISSE table is larger than the store, and the compact slot stays below 4 GiB (the kernels hold a store's tags
+// as a 32-bit distance from its lines).
+static bool lanes_store_layout(const zpq_model *m, uint32_t cap, DModel *layout)
+{
+    return zpq_lanes_supported(&m->d) && zpq_sparse_layout(m->d, cap, layout) && layout->slot_bytes < (1ull << 32);
+}
+extern "C" int zpq_lanes_store_applies(const zpq_model *m, uint32_t cap_lines) try
+{
+    DModel layout;
+    return m && lanes_store_layout(m, cap_lines, &layout) ? 1 : 0;
+} ZPQ_CATCH(return 0)
+extern "C" uint64_t zpq_lanes_store_slot_bytes(const zpq_model *m, uint32_t cap_lines) try
+{
+    DModel layout;
+    return m && lanes_store_layout(m, cap_lines, &layout) ? layout.slot_bytes : 0;
+} ZPQ_CATCH(return 0)
 // a model the chain kernels take
 static bool is_chain_model(const zpq_model *m) { return m->d.fast_kind && zpq_chain_blocks_per_wg(&m->d) > 0; }
 
@@ -574,6 +592,14 @@ static int plan_batch(zpq_ctx *c, const zpq_model *m, uint32_t flags, int nblock
             nslots = dn; grid = dg; bpw = db;
         }
     } else {
+        // the line store on request (never by itself: EXPERIMENTS.md R20).  ZPQ_SPARSE_FORCE_LOG2 counts only under the request
+        // here; a request that is not honoured decides nothing.  (zpq_block calls, ZB_NO_VMPIPE, make no requests.)
+        if (lanes && !(flags & ZB_NO_VMPIPE) && request("ZPQ_LANES_STORE", flags, ZPQ_FLAG_LINESTORE)) {
+            const SparseKnobs K = sparse_knobs();
+            const uint32_t cap = K.forced_cap ? K.forced_cap : c->sparse_cap;
+            DModel layout;
+            if (!K.never && lanes_store_layout(m, cap, &layout)) { P->sp = cap; P->M = layout; }
+        }
         const DModel &M = P->M;
         const uint64_t max_by_mem = M.slot_bytes ? (c->pool_budget() / M.slot_bytes) : (uint64_t)nblocks;
         if (max_by_mem == 0 && !own_slot) return ZPQ_E_NOMEM;
@@ -583,7 +609,8 @@ static int plan_batch(zpq_ctx *c, const zpq_model *m, uint32_t flags, int nblock
             // the wave pipelines where the model is in their envelope; the pair with an interpreter wave only on request
             // (ZPQ_FLAG_VMPIPE / ZPQ_VM_PIPE; a zpq_block's first segment keeps its kernel: ZB_NO_VMPIPE)
             const bool vm_pipe = !(flags & ZB_NO_VMPIPE) && request("ZPQ_VM_PIPE", flags, ZPQ_FLAG_VMPIPE);
-            if ((decode ? zpq_gdec_applies(&M) : zpq_gpipe_applies(&M)) != 0) P->fam = decode ? F_GDEC : F_GPIPE;
+            if (P->sp) P->fam = F_LANES;                           // (the wave pipelines have no store)
+            else if ((decode ? zpq_gdec_applies(&M) : zpq_gpipe_applies(&M)) != 0) P->fam = decode ? F_GDEC : F_GPIPE;
             else if (vm_pipe && (decode ? zpq_vdec_applies(&M) : zpq_vpipe_applies(&M)) != 0) P->fam = decode ? F_VDEC : F_VPIPE;
             else P->fam = F_LANES;
         }
@@ -1213,7 +1240,7 @@ static int block_segment(zpq_block *b, int decode, const uint8_t *in, size_t n, 
     if (!b->ctx) return ZPQ_E_CLOSED;                   // the block's ctx has been destroyed
     const uint64_t in_off[2] = {0, n}, out_off[2] = {0, cap};
     int32_t st = 0;
-    BlockArrays h = block_arrays(1, in, in_off, flags & 0xffu, out, out_off, &r->len, &st);
+    BlockArrays h = block_arrays(1, in, in_off, flags & 0xffu & ~ZPQ_FLAG_LINESTORE, out, out_off, &r->len, &st);
     if (decode) { h.consumed = &r->consumed; h.final_code = &r->code; h.first_byte = &r->first; }
     if (!(b->fresh && !(flags & ZPQ_FLAG_GENERIC))) {
         // a later segment (or the generic kernel asked for): on the block's own slot
@@ -1234,7 +1261,7 @@ static int block_segment(zpq_block *b, int decode, const uint8_t *in, size_t n, 
     if (st != ZPQ_OK) return st;                        // nothing persisted: the block is still fresh, the caller may retry
     b->fresh = false;
     b->lazy = true;
-    b->lazy_flags = flags & 0xffu;
+    b->lazy_flags = flags & 0xffu & ~ZPQ_FLAG_LINESTORE;
     if (!decode) { b->lazy_in.assign(in, in + n); return ZPQ_OK; }
     // the symbols this segment coded: [PP byte] + output.  With ZPQ_FLAG_PP the first symbol came back in `first`
     // (0xFFFFFFFF = the stream ended before it); a later encode replays 0 as the PP byte, anything else literally.
@@ -1517,7 +1544,7 @@ static int set_segments(zpq_blockset *s, int decode, const int32_t *member, cons
     }
     HIPCK(hipMemcpyAsync(S.misc.p, h_map.data(), u32b, hipMemcpyHostToDevice, st));
     if ((rc = stage_upload(S, k, st, false)) != ZPQ_OK) return rc;
-    BlockArrays dv = S.device_view(k, h.flags & 0xffu, decode);
+    BlockArrays dv = S.device_view(k, h.flags & 0xffu & ~ZPQ_FLAG_LINESTORE, decode);   // (a set's layout is its own: no request here)
     if (s->chain || (s->flags & ZPQ_SET_LANES)) {
         DevModel dm;
         if ((rc = get_dev_model(c, s->model, s->layout, s->sp, &dm)) != ZPQ_OK) return rc;

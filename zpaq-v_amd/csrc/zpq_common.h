@@ -103,7 +103,7 @@ struct DBatch {
 
 #define ZB_KEEP_STATE 0x100u     // do not re-initialise the slot (later segments of one block)
 #define ZB_CTX_ONLY 0x200u       // debug: run only the ZPAQL VM and dump contexts
-#define ZB_NO_VMPIPE 0x400u      // zpq_block: neither ZPQ_FLAG_VMPIPE nor ZPQ_VM_PIPE applies
+#define ZB_NO_VMPIPE 0x400u      // zpq_block: neither ZPQ_FLAG_VMPIPE / ZPQ_VM_PIPE nor ZPQ_FLAG_LINESTORE / ZPQ_LANES_STORE applies
 #define ZB_SET_PIPE 0x800u       // a block set's encode call (with ZB_KEEP_STATE) may run on k_pipe<..., KEEP> (ZPQ_SET_PIPE)
 // Chunk calls on a block set (zpq_blockset_{encode,decode}_chunks): a launch may stop in the middle of a segment and the next
 // one go on from there (compressor.v:259-293, decompressor.v:443-515).

@@ -92,6 +92,80 @@ __device__ __forceinline__ i32 wave_sum(i32 x)
                 wadd(__builtin_amdgcn_readlane(x, 47), __builtin_amdgcn_readlane(x, 63)));
 }
 
+// SP (k_lanes and k_rows, on request: ZPQ_FLAG_LINESTORE): a hashed component with C.sp_cap != 0 keeps its bit-history rows
+// in the compact line store (zpq_model.cpp zpq_sparse_layout) instead of a dense table, probed as zpq_chain.hip probes it:
+// key = dense line index + 1, home slot = mulhi(key * 0x9E3779B1, cap), tags in groups of four read with one 16-byte load,
+// the home group walked cyclically from the home slot, then the following groups.  find_ht's three candidate rows h0,
+// h0 ^ 16, h0 ^ 32 share one 64-byte line, so one probe per nibble serves them.  Every lane is another component with a
+// store, a claim count and a full flag of its own; dense and compact components meet in one wave.
+// sp_find: the slot of line `key`, given its home slot and the home group's tags T (loaded by the caller together with the
+// home line's rows).  A free slot met first is claimed: its tag is written here, SP_CLAIM tells the caller to zero the line.
+// Past cap - cap/16 claims (the chain kernels' limit), or with every slot taken, the block is refused (ZPQ_E_TOOBIG): the
+// lane walks and claims no more and goes on in the home slot's line -- in bounds, its output unspecified.
+// (SP) zpq_dev.h's slot_zero / slot_fill with their loops left rolled: unrolled, every loop keeps first + k * stride in
+// registers across the whole bit loop, which the store forms have no room for (they would spill them)
+__device__ __forceinline__ void slot_zero_rolled(const DModel &M, u8 *slot, const u32 first, const u32 stride)
+{
+    uint4 *z4 = reinterpret_cast<uint4 *>(slot);
+    const u64 n16 = M.zero_bytes / 16;
+    const uint4 zero = make_uint4(0, 0, 0, 0);
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    for (u64 i = first; i < n16; i += stride) z4[i] = zero;
+}
+__device__ __forceinline__ void slot_fill_rolled(const DModel &M, const u32 *img, u8 *slot, const u32 first, const u32 stride)
+{
+    for (i32 ci = 0; ci < M.n; ci++) {
+        const DComp &c = M.comp[ci];
+        const u32 cm_len = c.cm_len, fill = c.cm_fill, val = c.cm_fill_val, pat = c.cm_pat_len, a16_len = c.a16_len, a16_fill = c.a16_fill;
+        if (cm_len && fill != ZF_ZERO) {
+            u32 *t = reinterpret_cast<u32 *>(slot + c.cm_off);
+            if (fill == ZF_CONST) {
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+                for (u32 i = first; i < cm_len; i += stride) t[i] = val;
+            } else {
+                const u32 *im = img + val;
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+                for (u32 i = first; i < cm_len; i += stride) t[i] = im[i % pat];
+            }
+        }
+        if (a16_len && a16_fill) {
+            u16 *t = reinterpret_cast<u16 *>(slot + c.a16_off);
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+            for (u32 i = first; i < a16_len; i += stride) t[i] = (u16)a16_fill;
+        }
+    }
+}
+constexpr u32 SP_CLAIM = 0x80000000u;                            // (a slot index is below 2^25)
+constexpr u32 SP_FULL = 0xFFFFFFFFu;                             // claims: the store has refused the block (ZPQ_E_TOOBIG at its end)
+__device__ __forceinline__ u32 sp_find(u32 *tags, const u32 cap, const u32 key, const u32 home, u32x4 T, u32 &claims)
+{
+    const bool full = claims == SP_FULL;
+    const u32 o = home & 3u, groups = cap >> 2;
+    // slots of a group that end the probe -- the line's own tag, or a free slot -- as a mask rotated so that bit j stands
+    // for slot (o + j) & 3: the lowest set bit is the first such slot met
+    auto probe_group = [&](const u32x4 t) -> u32 {
+        const u32 mm = (min(t.x ^ key, t.x) == 0u ? 1u : 0u) | (min(t.y ^ key, t.y) == 0u ? 2u : 0u) |
+                       (min(t.z ^ key, t.z) == 0u ? 4u : 0u) | (min(t.w ^ key, t.w) == 0u ? 8u : 0u);
+        return ((mm * 17u) >> o) & 15u;
+    };
+    u32 g = home >> 2, r = probe_group(T);
+    if (r == 0u && !full)
+        for (u32 tries = 1; tries < groups; tries++) {
+            g = (g + 1u == groups) ? 0u : g + 1u;
+            T = *reinterpret_cast<const u32x4 *>(tags + 4u * g);
+            r = probe_group(T);
+            if (r) break;
+        }
+    const u32 idx = (o + (u32)__builtin_ctz(r | 16u)) & 3u;
+    const u32 t = (idx & 2u) ? ((idx & 1u) ? T.w : T.z) : ((idx & 1u) ? T.y : T.x);
+    const u32 si = 4u * g + idx;
+    if (r == 0u || (t == 0u && (full || claims >= cap - (cap >> 4)))) { claims = SP_FULL; return home; }
+    if (t != 0u) return si;
+    claims++;
+    tags[si] = key;
+    return si | SP_CLAIM;
+}
+
 // VMH: the program is the shipped hash chain (cfg.vm_hashes > 0), evaluated in registers -- such launches do not carry
 // the ZPAQL interpreter at all (fewer registers, no spills); any other program runs through it on lane 0.
 //
@@ -110,7 +184,28 @@ __device__ __forceinline__ i32 wave_sum(i32 x)
 // MIX / MIX2 / SSE entries never stay in registers beyond the bit that fetched them.  The format is the same for both
 // kernels: ZPQ_LANES_ROWS may change between two launches on one set.
 // (VMH stays the last template parameter: tests/test_kernel_resources.py finds the hash-chain instantiations by it.)
-template <bool DEC, bool KEEP, bool VMH>
+//
+// (SP) Registers.  The dense forms fill their 128 registers; the probe needs some.  A lane is one component for good, so a
+// register that only one component type uses can serve another type on other lanes, and the store forms share them:
+//   an SSE's four words               in v0, v1, st (ICM / ISSE / CM / MIX2 state) and mcur (MATCH)
+//   a MATCH's ma, mc, mcxt            in v1, st and cxt, which a MATCH does not use (ma and mc are read on every lane,
+//                                     masked, and used on a MATCH's alone)
+//   a hashed component's row offset   (roff: raddr as an offset from ht, dense table or line array) and its store's claim
+//   and claim count                   count (sp_claims; SP_FULL: it refused the block) in a MATCH's mb and mlimit, which
+//                                     start at 0 on such a lane
+// In the dense forms each name is the variable of its own that it was (own_*).  They are spelled as conditional lvalues on
+// the template parameter, not as references: the compiler emits the live arm alone, and the dense forms stay what they were
+// instruction for instruction (a reference, even to the same variable, reorders their registers).
+#define ma (SP ? reinterpret_cast<i32 &>(v1) : own_ma)
+#define mc (SP ? reinterpret_cast<i32 &>(st) : own_mc)
+#define mcxt (SP ? cxt : own_mcxt)
+#define sse_idx (SP ? mcur : own_sse_idx)
+#define sse_i0 (SP ? st : own_sse_i0)
+#define sse_v0 (SP ? v0 : own_sse_v0)
+#define sse_v1 (SP ? v1 : own_sse_v1)
+#define roff reinterpret_cast<u32 &>(mb)
+#define sp_claims reinterpret_cast<u32 &>(mlimit)
+template <bool DEC, bool KEEP, bool SP, bool VMH>
 __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const LCfg cfg)
 {
     extern __shared__ __align__(16) u8 lds[];
@@ -141,6 +236,9 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
 
     const int n = cfg.n;
     const int last = n - 1;
+    // (SP) the store forms fetch ahead for one MIX and one SSE only -- the registers of the second pay for the probe -- and
+    // take a second one as they take a third
+    const int mix1 = SP ? -1 : cfg.mix_ci[1], sse1 = SP ? -1 : cfg.sse_ci[1];
     const bool act = lane < n;
     const int slot_id = blockIdx.x * WAVES + wave;
     const int nslots = B.nslots;
@@ -157,6 +255,9 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
     u8 *ht = slot + C.ht_off;
     u16 *a16 = reinterpret_cast<u16 *>(slot + C.a16_off);
     const bool hashed = type == ZT_ICM || type == ZT_ISSE;
+    const u32 sp_cap = (SP && hashed) ? C.sp_cap : 0u;           // != 0: this lane's rows live in a line store, ht = its lines
+    const u32 sp_back = (u32)(C.sp_line_off - C.sp_tag_off);    // its tags lie this far in front of the lines (a compact slot is below 4 GiB)
+    if (SP && sp_cap) ht = slot + C.sp_line_off;
     const u32 cm_lo = (u32)(uintptr_t)cm, cm_hi = (u32)((u64)(uintptr_t)cm >> 32);
     auto tab_of = [&](int ci) -> u32 * {                          // component ci's u32 table, wave-uniform
         const u64 lo = (u32)__builtin_amdgcn_readlane((i32)cm_lo, ci), hi = (u32)__builtin_amdgcn_readlane((i32)cm_hi, ci);
@@ -177,16 +278,16 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
         // ---- Predictor.init + ZPAQL.clear (predictor.v:325-470, zpaql.v:54-95): the wave zeroes
         //      its slot with 16-B stores, then fills the non-zero tables
         if (!KEEP) {
-            slot_zero(M, slot, lane, 64);
+            if (SP) slot_zero_rolled(M, slot, lane, 64); else slot_zero(M, slot, lane, 64);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();
-            slot_fill(M, B.img, slot, lane, 64);
+            if (SP) slot_fill_rolled(M, B.img, slot, lane, 64); else slot_fill(M, B.img, slot, lane, 64);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         }
         const bool h_in_lds = M.hlen <= (u32)W_H_WORDS;
-        if (h_in_lds && !(KEEP && VMH)) for (u32 i = lane; i < M.hlen; i += 64) hl[i] = KEEP ? reinterpret_cast<const u32 *>(slot + M.h_off)[i] : 0u;
+        if (h_in_lds && !(KEEP && VMH) && !(SP && VMH)) for (u32 i = lane; i < M.hlen; i += 64) hl[i] = KEEP ? reinterpret_cast<const u32 *>(slot + M.h_off)[i] : 0u;
         for (int k = 0; k < 4; k++) reinterpret_cast<u32 *>(myrow)[k] = 0;
 
         const u8 *src = B.in + B.in_off[blk];
@@ -209,10 +310,13 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
         bool row_live = false;
         // MATCH: a = len, b = offset, c = predicted bit, cxt = bit position, limit = buffer position.
         // Quirk: init leaves sizebits/bufbits in a/b (predictor.v:372-373,566-572).
-        i32 ma = (type == ZT_MATCH) ? ca : 0, mb = (type == ZT_MATCH) ? cb : 0, mc = 0, mlimit = 0;
-        u32 mcxt = 0, mcur = 0;                               // mcur mirrors ht[limit], the byte being shifted in
+        // (ma, mc, mcxt and the SSE's four words below: registers of their own in the dense forms, shared ones under SP -- see
+        //  the #defines in front of this kernel)
+        i32 own_ma = (type == ZT_MATCH) ? ca : 0, mb = (type == ZT_MATCH) ? cb : 0, own_mc = 0, mlimit = 0;
+        u32 own_mcxt = 0, mcur = 0;                           // mcur mirrors ht[limit], the byte being shifted in
+        if (SP) ma = own_ma;
         // SSE keeps both table entries it interpolated between
-        u32 sse_idx = 0, sse_i0 = 0, sse_v0 = 0, sse_v1 = 0;
+        u32 own_sse_idx = 0, own_sse_i0 = 0, own_sse_v0 = 0, own_sse_v1 = 0;
         bool sse_ok = false;
 
         u32 c8 = 1, hmap4 = 1, vm_prev = 0;
@@ -275,16 +379,44 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
                         const u32 chk = (cx >> (ca + 2)) & 255u;
                         const u32 h0 = (cx * 16u) & (ht_len - 16u);
                         u8 *pa = ht + h0, *pb = ht + (h0 ^ 16u), *pc = ht + (h0 ^ 32u);
-                        const u32x4 A = *reinterpret_cast<const u32x4 *>(pa);
-                        const u32x4 Bq = *reinterpret_cast<const u32x4 *>(pb);
-                        const u32x4 Cq = *reinterpret_cast<const u32x4 *>(pc);
+                        u32 sp_home = 0;
+                        if (SP) roff = h0;
+                        u32x4 sp_T = {0, 0, 0, 0};
+                        u32 *sp_tags = reinterpret_cast<u32 *>(ht - sp_back);
+                        if (SP && sp_cap) {                          // the home group's tags and the home line's rows in one round trip
+                            sp_home = __umulhi(((h0 >> 6) + 1u) * 0x9E3779B1u, sp_cap);
+                            sp_T = *reinterpret_cast<const u32x4 *>(sp_tags + (sp_home & ~3u));
+                            const u32 po = (sp_home << 6) + (h0 & 48u);
+                            pa = ht + po; pb = ht + (po ^ 16u); pc = ht + (po ^ 32u);
+                        }
+                        u32x4 A = *reinterpret_cast<const u32x4 *>(pa);
+                        u32x4 Bq = *reinterpret_cast<const u32x4 *>(pb);
+                        u32x4 Cq = *reinterpret_cast<const u32x4 *>(pc);
+                        if (SP && sp_cap) {
+                            const u32 sf = sp_find(sp_tags, sp_cap, (h0 >> 6) + 1u, sp_home, sp_T, sp_claims);
+                            const u32 si = sf & ~SP_CLAIM;
+                            const u32 po = (si << 6) + (h0 & 48u);
+                            pa = ht + po; pb = ht + (po ^ 16u); pc = ht + (po ^ 32u);
+                            roff = po;
+                            if (sf & SP_CLAIM) {                     // a new line starts out all zero, like an untouched dense line
+                                const u32x4 z4 = {0, 0, 0, 0};
+                                u32x4 *ln = reinterpret_cast<u32x4 *>(ht + (si << 6));
+                                ln[0] = z4; ln[1] = z4; ln[2] = z4; ln[3] = z4;
+                                A = z4; Bq = z4; Cq = z4;
+                            } else if (si != sp_home) {              // displaced when it was claimed: its rows were not the ones fetched
+                                A = *reinterpret_cast<const u32x4 *>(pa);
+                                Bq = *reinterpret_cast<const u32x4 *>(pb);
+                                Cq = *reinterpret_cast<const u32x4 *>(pc);
+                            }
+                        }
                         const bool ma_ = (A.x & 255u) == chk, mb_ = (Bq.x & 255u) == chk, mc_ = (Cq.x & 255u) == chk;
                         const u32 qa = (A.x >> 8) & 255u, qb = (Bq.x >> 8) & 255u, qc = (Cq.x >> 8) & 255u;
                         const bool va = qa <= qb && qa <= qc, vb = qb < qc;
                         const bool hit = ma_ || mb_ || mc_;
                         const bool ua = ma_ || (!hit && va);
                         const bool ub = !ua && (mb_ || (!hit && vb));
-                        raddr = ua ? pa : (ub ? pb : pc);
+                        if (SP) roff = ua ? roff : (ub ? roff ^ 16u : roff ^ 32u);   // (SP: the row's offset from ht, dense or compact)
+                        else raddr = ua ? pa : (ub ? pb : pc);
                         const u32x4 Rr = ua ? A : (ub ? Bq : Cq);
                         u32 *rw = reinterpret_cast<u32 *>(myrow);
                         rw[0] = hit ? Rr.x : chk; rw[1] = hit ? Rr.y : 0u; rw[2] = hit ? Rr.z : 0u; rw[3] = hit ? Rr.w : 0u;
@@ -314,8 +446,8 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
                     const i32 l = (lane - idx) & 63;
                     if (l < m && (j + l) < n) { pj0 = j + l; pa0 = tab_of(ci) + (idx + l); pw0 = *pa0; }
                 }
-                if (cfg.mix_ci[1] >= 0) {
-                    const int ci = cfg.mix_ci[1];
+                if (mix1 >= 0) {
+                    const int ci = mix1;
                     const i32 j = __builtin_amdgcn_readlane(cb, ci), m = __builtin_amdgcn_readlane(climit, ci);
                     const i32 idx = wmul((i32)__builtin_amdgcn_readlane((i32)cxt, ci), m);
                     const i32 l = (lane - idx) & 63;
@@ -326,8 +458,8 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
                     const i32 il = wadd((i32)__builtin_amdgcn_readlane((i32)cxt, ci), lane);
                     if (lane < 32 && il >= 0 && il < (i32)__builtin_amdgcn_readlane((i32)cm_len, ci)) sr0 = tab_of(ci)[il];
                 }
-                if (cfg.sse_ci[1] >= 0) {
-                    const int ci = cfg.sse_ci[1];
+                if (sse1 >= 0) {
+                    const int ci = sse1;
                     const i32 il = wadd((i32)__builtin_amdgcn_readlane((i32)cxt, ci), lane);
                     if (lane < 32 && il >= 0 && il < (i32)__builtin_amdgcn_readlane((i32)cm_len, ci)) sr1 = tab_of(ci)[il];
                 }
@@ -367,7 +499,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
                             const i32 t = __shfl(merged, pj0 & 63);
                             pin0 = pj0 >= 0 ? t : 0;
                             part = wmul((i32)pw0 >> 8, pin0);
-                        } else if (ci == cfg.mix_ci[1]) {
+                        } else if (ci == mix1) {
                             const i32 t = __shfl(merged, pj1 & 63);
                             pin1 = pj1 >= 0 ? t : 0;
                             part = wmul((i32)pw1 >> 8, pin1);
@@ -406,7 +538,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
                         pq = min(max(pq, 0), 1983);
                         const i32 wt = pq & 63;
                         pq >>= 6;
-                        const bool pre0 = ci == cfg.sse_ci[0], pre1 = ci == cfg.sse_ci[1];
+                        const bool pre0 = ci == cfg.sse_ci[0], pre1 = ci == sse1;
                         // prefetched row: entry e sits in lane e
                         const u32 srow = pre0 ? sr0 : sr1;
                         const u32 e0 = (u32)__builtin_amdgcn_readlane((i32)srow, pq), e1 = (u32)__builtin_amdgcn_readlane((i32)srow, pq + 1);
@@ -512,7 +644,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
                     if (ci == cfg.mix_ci[0]) {
                         const i32 fin = __shfl(pown, pj0 & 63);
                         if (pj0 >= 0) *pa0 = (u32)clamp512k(wadd((i32)pw0, wadd(wmul(err, fin), 1 << 12) >> 13));
-                    } else if (ci == cfg.mix_ci[1]) {
+                    } else if (ci == mix1) {
                         const i32 fin = __shfl(pown, pj1 & 63);
                         if (pj1 >= 0) *pa1 = (u32)clamp512k(wadd((i32)pw1, wadd(wmul(err, fin), 1 << 12) >> 13));
                     } else {
@@ -528,7 +660,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
                 // ================= E. bit context (predictor.v:807-823) =================
                 c8 = (c8 << 1) | (u32)y;
                 const bool nib_end = (bit & 3) == 0;
-                if (nib_end && hashed && row_live) *reinterpret_cast<u32x4 *>(raddr) = *reinterpret_cast<const u32x4 *>(myrow);
+                if (nib_end && hashed && row_live) *reinterpret_cast<u32x4 *>(SP ? ht + roff : raddr) = *reinterpret_cast<const u32x4 *>(myrow);
                 if (c8 >= 256) {
                     /* byte boundary handled below */
                 } else if (c8 >= 16 && c8 < 32) hmap4 = ((hmap4 & 0xfu) << 5) | ((u32)y << 4) | 1u;
@@ -593,8 +725,11 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
             if (h_in_lds && !VMH) for (u32 i = lane; i < M.hlen; i += 64) reinterpret_cast<u32 *>(slot + M.h_off)[i] = hl[i];
         }
         const i32 st0 = __builtin_amdgcn_readlane(status, 0);
+        // (SP) a store's refusal arises on its component's lane: any lane of the block; behind the step cap, ahead of the slab
+        const bool sp_refused = SP && __builtin_amdgcn_ballot_w64(sp_claims == SP_FULL) != 0;
         if (lane == last) {
             i32 stt = st0;
+            if (SP && sp_refused && stt == ZPQ_OK) stt = ZPQ_E_TOOBIG;
             if (opos > cap && stt == ZPQ_OK) stt = ZPQ_E_OVERFLOW;
             B.out_len[blk] = opos;
             B.status[blk] = stt;
@@ -634,7 +769,7 @@ __device__ __forceinline__ i32 row_sum_all(i32 x, int rb)
 
 // VMH as in k_lanes: true = the shipped hash chain, evaluated in registers; false = any program, through the shared
 // interpreter on lane 0 of every ROW (four interpreters per wave walking the same program on their own blocks' bytes).
-template <bool DEC, bool KEEP = false, bool VMH = true>
+template <bool DEC, bool KEEP = false, bool SP = false, bool VMH = true>
 __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B, const LCfg cfg)
 {
     extern __shared__ __align__(16) u8 lds[];
@@ -665,6 +800,9 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
 
     const int n = cfg.n;
     const int last = n - 1;
+    // (SP) the store forms fetch ahead for one MIX and one SSE only -- the registers of the second pay for the probe -- and
+    // take a second one as they take a third
+    const int mix1 = SP ? -1 : cfg.mix_ci[1], sse1 = SP ? -1 : cfg.sse_ci[1];
     const bool act = li < n;
     const int slot_id = (blockIdx.x * WAVES + wave) * RPW + row;
     const int nslots = B.nslots;
@@ -680,6 +818,9 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
     u8 *ht = slot + C.ht_off;
     u16 *a16 = reinterpret_cast<u16 *>(slot + C.a16_off);
     const bool hashed = type == ZT_ICM || type == ZT_ISSE;
+    const u32 sp_cap = (SP && hashed) ? C.sp_cap : 0u;           // != 0: this lane's rows live in a line store, ht = its lines
+    const u32 sp_back = (u32)(C.sp_line_off - C.sp_tag_off);    // its tags lie this far in front of the lines (a compact slot is below 4 GiB)
+    if (SP && sp_cap) ht = slot + C.sp_line_off;
     // Model constants of component ci: lane ci of ROW 0 holds them in registers (every row carries the same model), so
     // v_readlane hands them out as scalars -- no scalar memory load of M.comp[ci] per bit.
     const u32 cmo_lo = (u32)C.cm_off, cmo_hi = (u32)(C.cm_off >> 32);
@@ -702,10 +843,10 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
 
     for (int blk = slot_id; slot_id < nslots && blk < B.nblocks; blk += nslots) {
         if (!KEEP) {   // Predictor.init + ZPAQL.clear: the row zeroes its slot, then fills the non-zero tables
-            slot_zero(M, slot, li, RL);
+            if (SP) slot_zero_rolled(M, slot, li, RL); else slot_zero(M, slot, li, RL);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();
-            slot_fill(M, B.img, slot, li, RL);
+            if (SP) slot_fill_rolled(M, B.img, slot, li, RL); else slot_fill(M, B.img, slot, li, RL);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -729,9 +870,10 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
         i32 pown = 0;
         u8 *raddr = ht;
         bool row_live = false;
-        i32 ma = (type == ZT_MATCH) ? ca : 0, mb = (type == ZT_MATCH) ? cb : 0, mc = 0, mlimit = 0;   // quirk Q17
-        u32 mcxt = 0, mcur = 0;
-        u32 sse_idx = 0, sse_i0 = 0, sse_v0 = 0, sse_v1 = 0;
+        i32 own_ma = (type == ZT_MATCH) ? ca : 0, mb = (type == ZT_MATCH) ? cb : 0, own_mc = 0, mlimit = 0;   // quirk Q17
+        u32 own_mcxt = 0, mcur = 0;
+        if (SP) ma = own_ma;
+        u32 own_sse_idx = 0, own_sse_i0 = 0, own_sse_v0 = 0, own_sse_v1 = 0;
         bool sse_ok = false;
 
         u32 c8 = 1, hmap4 = 1, vm_prev = 0;
@@ -785,16 +927,44 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
                         const u32 chk = (cx >> (ca + 2)) & 255u;
                         const u32 h0 = (cx * 16u) & (ht_len - 16u);
                         u8 *pa = ht + h0, *pb = ht + (h0 ^ 16u), *pc = ht + (h0 ^ 32u);
-                        const u32x4 A = *reinterpret_cast<const u32x4 *>(pa);
-                        const u32x4 Bq = *reinterpret_cast<const u32x4 *>(pb);
-                        const u32x4 Cq = *reinterpret_cast<const u32x4 *>(pc);
+                        u32 sp_home = 0;
+                        if (SP) roff = h0;
+                        u32x4 sp_T = {0, 0, 0, 0};
+                        u32 *sp_tags = reinterpret_cast<u32 *>(ht - sp_back);
+                        if (SP && sp_cap) {                          // the home group's tags and the home line's rows in one round trip
+                            sp_home = __umulhi(((h0 >> 6) + 1u) * 0x9E3779B1u, sp_cap);
+                            sp_T = *reinterpret_cast<const u32x4 *>(sp_tags + (sp_home & ~3u));
+                            const u32 po = (sp_home << 6) + (h0 & 48u);
+                            pa = ht + po; pb = ht + (po ^ 16u); pc = ht + (po ^ 32u);
+                        }
+                        u32x4 A = *reinterpret_cast<const u32x4 *>(pa);
+                        u32x4 Bq = *reinterpret_cast<const u32x4 *>(pb);
+                        u32x4 Cq = *reinterpret_cast<const u32x4 *>(pc);
+                        if (SP && sp_cap) {
+                            const u32 sf = sp_find(sp_tags, sp_cap, (h0 >> 6) + 1u, sp_home, sp_T, sp_claims);
+                            const u32 si = sf & ~SP_CLAIM;
+                            const u32 po = (si << 6) + (h0 & 48u);
+                            pa = ht + po; pb = ht + (po ^ 16u); pc = ht + (po ^ 32u);
+                            roff = po;
+                            if (sf & SP_CLAIM) {                     // a new line starts out all zero, like an untouched dense line
+                                const u32x4 z4 = {0, 0, 0, 0};
+                                u32x4 *ln = reinterpret_cast<u32x4 *>(ht + (si << 6));
+                                ln[0] = z4; ln[1] = z4; ln[2] = z4; ln[3] = z4;
+                                A = z4; Bq = z4; Cq = z4;
+                            } else if (si != sp_home) {              // displaced when it was claimed: its rows were not the ones fetched
+                                A = *reinterpret_cast<const u32x4 *>(pa);
+                                Bq = *reinterpret_cast<const u32x4 *>(pb);
+                                Cq = *reinterpret_cast<const u32x4 *>(pc);
+                            }
+                        }
                         const bool ma_ = (A.x & 255u) == chk, mb_ = (Bq.x & 255u) == chk, mc_ = (Cq.x & 255u) == chk;
                         const u32 qa = (A.x >> 8) & 255u, qb = (Bq.x >> 8) & 255u, qc = (Cq.x >> 8) & 255u;
                         const bool va = qa <= qb && qa <= qc, vb = qb < qc;
                         const bool hit = ma_ || mb_ || mc_;
                         const bool ua = ma_ || (!hit && va);
                         const bool ub = !ua && (mb_ || (!hit && vb));
-                        raddr = ua ? pa : (ub ? pb : pc);
+                        if (SP) roff = ua ? roff : (ub ? roff ^ 16u : roff ^ 32u);   // (SP: the row's offset from ht, dense or compact)
+                        else raddr = ua ? pa : (ub ? pb : pc);
                         u32 *rw = reinterpret_cast<u32 *>(myrow);
                         rw[0] = hit ? (ua ? A.x : (ub ? Bq.x : Cq.x)) : chk;
                         rw[1] = hit ? (ua ? A.y : (ub ? Bq.y : Cq.y)) : 0u;
@@ -826,8 +996,8 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
                     const i32 l = (li - idx) & (RL - 1);
                     if (l < m && (j + l) < n) { pj0 = j + l; pa0 = tab_of(ci) + (idx + l); pw0 = *pa0; }
                 }
-                if (cfg.mix_ci[1] >= 0) {
-                    const int ci = cfg.mix_ci[1];
+                if (mix1 >= 0) {
+                    const int ci = mix1;
                     const i32 j = cst(cb, ci), m = cst(climit, ci);
                     const i32 idx = wmul(rowget((i32)cxt, ci), m);
                     const i32 l = (li - idx) & (RL - 1);
@@ -840,8 +1010,8 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
                     if (ia >= 0 && ia < len) srA0 = tab_of(ci)[ia];
                     if (ib >= 0 && ib < len) srB0 = tab_of(ci)[ib];
                 }
-                if (cfg.sse_ci[1] >= 0) {
-                    const int ci = cfg.sse_ci[1];
+                if (sse1 >= 0) {
+                    const int ci = sse1;
                     const i32 base = rowget((i32)cxt, ci), len = cst((i32)cm_len, ci);
                     const i32 ia = wadd(base, li), ib = wadd(base, li + RL);
                     if (ia >= 0 && ia < len) srA1 = tab_of(ci)[ia];
@@ -872,7 +1042,7 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
                             const i32 t = rowget(merged, pj0);
                             pin0 = pj0 >= 0 ? t : 0;
                             part = wmul((i32)pw0 >> 8, pin0);
-                        } else if (ci == cfg.mix_ci[1]) {
+                        } else if (ci == mix1) {
                             const i32 t = rowget(merged, pj1);
                             pin1 = pj1 >= 0 ? t : 0;
                             part = wmul((i32)pw1 >> 8, pin1);
@@ -911,7 +1081,7 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
                         pq = min(max(pq, 0), 1983);
                         const i32 wt = pq & 63;
                         pq >>= 6;
-                        const bool pre0 = ci == cfg.sse_ci[0], pre1 = ci == cfg.sse_ci[1];
+                        const bool pre0 = ci == cfg.sse_ci[0], pre1 = ci == sse1;
                         // prefetched row: entry e sits in lane e & 15 of the row, register e >> 4
                         const u32 sA = pre0 ? srA0 : srA1, sB = pre0 ? srB0 : srB1;
                         const u32 e0a = (u32)rowget((i32)sA, pq), e0b = (u32)rowget((i32)sB, pq);
@@ -1015,7 +1185,7 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
                     if (ci == cfg.mix_ci[0]) {
                         const i32 fin = rowget(pown, pj0);
                         if (pj0 >= 0) *pa0 = (u32)clamp512k(wadd((i32)pw0, wadd(wmul(err, fin), 1 << 12) >> 13));
-                    } else if (ci == cfg.mix_ci[1]) {
+                    } else if (ci == mix1) {
                         const i32 fin = rowget(pown, pj1);
                         if (pj1 >= 0) *pa1 = (u32)clamp512k(wadd((i32)pw1, wadd(wmul(err, fin), 1 << 12) >> 13));
                     } else {
@@ -1030,7 +1200,7 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
                 // ================= E. bit context =================
                 c8 = (c8 << 1) | (u32)y;
                 const bool nib_end = (bit & 3) == 0;
-                if (nib_end && hashed && row_live) *reinterpret_cast<u32x4 *>(raddr) = *reinterpret_cast<const u32x4 *>(myrow);
+                if (nib_end && hashed && row_live) *reinterpret_cast<u32x4 *>(SP ? ht + roff : raddr) = *reinterpret_cast<const u32x4 *>(myrow);
                 if (c8 >= 256) {
                 } else if (c8 >= 16 && c8 < 32) hmap4 = ((hmap4 & 0xfu) << 5) | ((u32)y << 4) | 1u;
                 else hmap4 = (hmap4 & 0x1f0u) | (((hmap4 & 0xfu) * 2u + (u32)y) & 0xfu);
@@ -1079,8 +1249,11 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
             }
         }
         const i32 vm_st = VMH ? (i32)ZPQ_OK : rowget(vm_status, 0);   // (the interpreter's step cap: lane 0 of the row)
+        // (SP) a store's refusal arises on its component's lane: any lane of the row; behind the step cap, ahead of the slab
+        const bool sp_refused = SP && ((__builtin_amdgcn_ballot_w64(sp_claims == SP_FULL) >> rb) & 0xFFFFull) != 0;
         if (li == last) {
             i32 stt = vm_st;
+            if (SP && sp_refused && stt == ZPQ_OK) stt = ZPQ_E_TOOBIG;
             if (opos > cap && stt == ZPQ_OK) stt = ZPQ_E_OVERFLOW;
             B.out_len[blk] = opos;
             B.status[blk] = stt;
@@ -1095,6 +1268,16 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
         if (KEEP) break;                                          // one block per slot and launch
     }
 }
+
+#undef ma
+#undef mc
+#undef mcxt
+#undef sse_idx
+#undef sse_i0
+#undef sse_v0
+#undef sse_v1
+#undef roff
+#undef sp_claims
 
 // Predictor.init + ZPAQL.clear (predictor.v:325-470, zpaql.v:54-95) of every member of a block set in one launch, in the
 // form the KEEP kernels load: the slot zeroed, the ZF_CONST / ZF_PATTERN tables and the a16 tables filled, MATCH's
@@ -1148,13 +1331,22 @@ static bool rows_ok(const zpql::LCfg &cfg)
     return cfg.n <= zpql::RL;
 }
 
+// a layout with a compact line store in it (zpq_sparse_layout; plan_batch hands one over only under ZPQ_FLAG_LINESTORE):
+// the batch launches below then take the store forms of the kernels
+static bool has_store(const DModel *M)
+{
+    for (int i = 0; i < M->n; i++) if (M->comp[i].sp_cap) return true;
+    return false;
+}
+
 extern "C" int zpq_lanes_blocks_per_cu(const DModel *M)
 {
     zpql::LCfg cfg;
-    const bool rows = lanes_cfg(M, &cfg) && rows_ok(cfg);
+    const bool rows = lanes_cfg(M, &cfg) && rows_ok(cfg), vmh = cfg.vm_hashes > 0;
+    const void *k = rows ? (vmh ? (const void *)zpql::k_rows<false, false, false, true> : (const void *)zpql::k_rows<false, false, false, false>) : (const void *)zpql::k_lanes<false, false, false, false>;
+    if (has_store(M)) k = rows ? (vmh ? (const void *)zpql::k_rows<false, false, true, true> : (const void *)zpql::k_rows<false, false, true, false>) : (const void *)zpql::k_lanes<false, false, true, false>;
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rows ? (cfg.vm_hashes > 0 ? (const void *)zpql::k_rows<false, false, true> : (const void *)zpql::k_rows<false, false, false>) : (const void *)zpql::k_lanes<false, false, false>,
-                                                     64 * zpql::WAVES, zpql::LDS_TOTAL) != hipSuccess || nb < 1)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 64 * zpql::WAVES, zpql::LDS_TOTAL) != hipSuccess || nb < 1)
         nb = 2;
     return nb * zpql::WAVES * (rows ? zpql::RPW : 1);
 }
@@ -1184,18 +1376,18 @@ extern "C" int zpq_launch_lanes_keep(const DBatch *B, const DModel *hostM, int d
     const dim3 g((B->nblocks + per_wg - 1) / per_wg), t(64 * zpql::WAVES);
     if (rows) {
         if (vmh) {
-            if (decode) hipLaunchKernelGGL((zpql::k_rows<true, true, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
-            else hipLaunchKernelGGL((zpql::k_rows<false, true, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+            if (decode) hipLaunchKernelGGL((zpql::k_rows<true, true, false, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+            else hipLaunchKernelGGL((zpql::k_rows<false, true, false, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
         } else {
-            if (decode) hipLaunchKernelGGL((zpql::k_rows<true, true, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
-            else hipLaunchKernelGGL((zpql::k_rows<false, true, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+            if (decode) hipLaunchKernelGGL((zpql::k_rows<true, true, false, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+            else hipLaunchKernelGGL((zpql::k_rows<false, true, false, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
         }
     } else if (vmh) {
-        if (decode) hipLaunchKernelGGL((zpql::k_lanes<true, true, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
-        else hipLaunchKernelGGL((zpql::k_lanes<false, true, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+        if (decode) hipLaunchKernelGGL((zpql::k_lanes<true, true, false, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+        else hipLaunchKernelGGL((zpql::k_lanes<false, true, false, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
     } else {
-        if (decode) hipLaunchKernelGGL((zpql::k_lanes<true, true, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
-        else hipLaunchKernelGGL((zpql::k_lanes<false, true, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+        if (decode) hipLaunchKernelGGL((zpql::k_lanes<true, true, false, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+        else hipLaunchKernelGGL((zpql::k_lanes<false, true, false, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
     }
     return ZPQ_OK;
 }
@@ -1204,26 +1396,21 @@ extern "C" int zpq_launch_lanes(const DBatch *B, const DModel *hostM, int decode
 {
     zpql::LCfg cfg;
     if (!lanes_cfg(hostM, &cfg)) return ZPQ_E_INTERNAL;
-    if (rows_ok(cfg)) {
-        const int per_wg = zpql::WAVES * zpql::RPW;
-        const dim3 g((nslots + per_wg - 1) / per_wg), t(64 * zpql::WAVES);
-        if (cfg.vm_hashes > 0) {
-            if (decode) hipLaunchKernelGGL((zpql::k_rows<true, false, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
-            else hipLaunchKernelGGL((zpql::k_rows<false, false, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
-        } else {
-            if (decode) hipLaunchKernelGGL((zpql::k_rows<true, false, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
-            else hipLaunchKernelGGL((zpql::k_rows<false, false, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
-        }
-        return ZPQ_OK;
-    }
-    const int grid = (nslots + zpql::WAVES - 1) / zpql::WAVES;
-    const dim3 g(grid), t(64 * zpql::WAVES);
-    if (cfg.vm_hashes > 0) {
-        if (decode) hipLaunchKernelGGL((zpql::k_lanes<true, false, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
-        else hipLaunchKernelGGL((zpql::k_lanes<false, false, true>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+    const bool rows = rows_ok(cfg), vmh = cfg.vm_hashes > 0, sp = has_store(hostM);
+    const int per_wg = zpql::WAVES * (rows ? zpql::RPW : 1);
+    const dim3 g((nslots + per_wg - 1) / per_wg), t(64 * zpql::WAVES);
+#define ZPQ_LANES_GO(K, SP_, VMH_)                                                                                    \
+    do {                                                                                                              \
+        if (decode) hipLaunchKernelGGL((zpql::K<true, false, SP_, VMH_>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);     \
+        else hipLaunchKernelGGL((zpql::K<false, false, SP_, VMH_>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);           \
+    } while (0)
+    if (rows) {
+        if (sp) { if (vmh) ZPQ_LANES_GO(k_rows, true, true); else ZPQ_LANES_GO(k_rows, true, false); }
+        else { if (vmh) ZPQ_LANES_GO(k_rows, false, true); else ZPQ_LANES_GO(k_rows, false, false); }
     } else {
-        if (decode) hipLaunchKernelGGL((zpql::k_lanes<true, false, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
-        else hipLaunchKernelGGL((zpql::k_lanes<false, false, false>), g, t, zpql::LDS_TOTAL, stream, *B, cfg);
+        if (sp) { if (vmh) ZPQ_LANES_GO(k_lanes, true, true); else ZPQ_LANES_GO(k_lanes, true, false); }
+        else { if (vmh) ZPQ_LANES_GO(k_lanes, false, true); else ZPQ_LANES_GO(k_lanes, false, false); }
     }
+#undef ZPQ_LANES_GO
     return ZPQ_OK;
 }
