@@ -39,6 +39,7 @@
 #include "zpq_host.h"
 #include "zpq_chain_cfg.h"
 #include "zpq_dev.h"
+#include "zpq_rows.h"
 
 // Measured on MI355X: the pipelined step wins for encode, for decode the step with
 // fewer instructions wins (both-candidate speculation was slower every time it was tried).
@@ -487,19 +488,11 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             return v;
         };
 
-        // find_ht (predictor.v:495-532): the three candidate rows h0, h0^16, h0^32 share one
-        // 64-byte line.  select_row resolves hit / victim with selects only.
+        // find_ht (zpq_rows.h): hit / victim among the three candidate rows, into the lane's row registers
         auto select_row = [&](const u32x4 A, const u32x4 Bq, const u32x4 Cq, const u32 pa, const u32 chk) {
-            const u32 pb = pa ^ 16u, pc = pa ^ 32u;                             // rows share a 64-B aligned line
-            const bool ma = (A.x & 255u) == chk, mb = (Bq.x & 255u) == chk, mc = (Cq.x & 255u) == chk;
-            const u32 qa = (A.x >> 8) & 255u, qb = (Bq.x >> 8) & 255u, qc = (Cq.x >> 8) & 255u;
-            const bool va = qa <= qb && qa <= qc, vb = qb < qc;            // victim order (predictor.v:513-531)
-            const bool hit = ma || mb || mc;
-            const bool ua = ma || (!hit && va);
-            const bool ub = !ua && (mb || (!hit && vb));
-            roff = ua ? pa : (ub ? pb : pc);
-            const u32x4 Rr = ua ? A : (ub ? Bq : Cq);
-            X.r0 = hit ? Rr.x : chk; X.r1 = hit ? Rr.y : 0u; X.r2 = hit ? Rr.z : 0u; X.r3 = hit ? Rr.w : 0u;
+            const Row R = find_row(Cands{A, Bq, Cq}, chk, pa, pa ^ 16u, pa ^ 32u);
+            roff = R.off;
+            X.r0 = R.x; X.r1 = R.y; X.r2 = R.z; X.r3 = R.w;
         };
         // Rows are requested AHEAD of the nibble that uses them.  Encode: every context is a
         // function of input bytes only, so the request goes out one whole nibble early and the
@@ -518,13 +511,15 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
         if constexpr (KEEP && SP) {
             if (hashed) { sp_claims = (u32)kscal->a; sp_full = kscal->b != 0; }
         }
-        const u32 sp_limit = sp_cap - (sp_cap >> 4);       // a block that needs more than 15/16 of the store is refused
+        const u32 sp_limit = ZPQ_SP_LIMIT(sp_cap);
         // second request of the non-HYP decoders (see TWO below): the rows for the other outcome of the nibble's last bit
         u32x4 aA = {0, 0, 0, 0}, aB = {0, 0, 0, 0}, aC = {0, 0, 0, 0}, a_tags = {0, 0, 0, 0};
         u32 a_po = 0, a_chk = 0, a_key = 0, a_si = 0, a_off = 0;
         bool sel_alt = false;                              // the nibble that really follows is the one the alt request was for
         // (a macro, not a lambda taking references: locals handed on by reference through a second closure are not
         //  promoted to registers -- the whole probe state ended up in scratch, 5x slower)
+        // (zpq_rows.h's load_cands, in place: the rows go into six separate locals here, and handed over in a Cands one
+        //  select of the level 3 / 4 line-store decoders for block sets moved)
 #ifdef ZPQ_DEBUG_NO_ROWS   // timing experiment only (wrong output): no hash-row traffic at all
 #define ZPQ_LOAD_ROWS(A_, B_, C_, po_) do { A_ = u32x4{(po_), 0, 0, 0}; B_ = A_; C_ = A_; } while (0)
 #else
@@ -535,23 +530,16 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
         C_ = *reinterpret_cast<const u32x4 *>(tbase + ((po_) ^ 32u));                   \
     } while (0)
 #endif
-        // Dense line index -> slot of the compact store.  Open addressing over GROUPS of four slots: the home
-        // slot is mulhi(hash, cap) (capacity need not be a power of two); probing visits the home group's
-        // slots cyclically from the home slot, then the following groups the same way.  One 16-byte load
-        // brings the home group's four tags, and the HOME slot's rows are fetched with them: a line that
-        // sits in its home slot, or a new line (it takes the first free slot it meets, and a new line is all
-        // zero -- nothing to load), costs one memory round trip; only a line that was displaced when it
-        // was claimed needs a second one for its rows, and only a full group is walked past.
+        // a request: the dense table's rows, or (the line store, zpq_rows.h) the home group's tags and the home slot's rows
 #define ZPQ_PREFETCH(A_, B_, C_, tags_, po_, chk_, key_, si_, off_, hc_, c8v_)          \
     do {                                                                                \
-        const u32 cx_ = (hc_) + 16u * (c8v_);                                           \
-        chk_ = (cx_ >> sizebits) & 255u;                                                \
-        const u32 h0_ = (cx_ * 16u) & ht_mask;                                          \
-        u32 pox_ = SWZ ? swz_addr(h0_) : h0_;                                           \
+        const RowReq rq_ = row_request((hc_), (c8v_), sizebits, ht_mask);               \
+        chk_ = rq_.chk;                                                                 \
+        u32 pox_ = SWZ ? swz_addr(rq_.h0) : rq_.h0;                                     \
         if (SPARSE && sp_cap) {                                                         \
-            key_ = (h0_ >> 6) + 1u;                                                     \
-            si_ = __umulhi(key_ * 0x9E3779B1u, sp_cap);                                 \
-            off_ = h0_ & 48u;                                                           \
+            key_ = sp_key(rq_.h0);                                                      \
+            si_ = sp_home(key_, sp_cap);                                                \
+            off_ = rq_.h0 & 48u;                                                        \
             tags_ = *reinterpret_cast<const u32x4 *>(sp_tags + (si_ & ~3u));            \
             pox_ = (si_ << 6) + off_;                                                   \
         }                                                                               \
@@ -612,28 +600,7 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             // would fill the store with lines no context owns) and takes the result over below
             const bool sp_act = !HYP || row_mine;
             if (SPARSE && sp_cap) {
-                const u32 o = n_si & 3u;
-                // slots of a group that end the probe -- the line's own tag, or a free slot -- as a 4-bit mask rotated
-                // so that bit j stands for slot (o + j) & 3: the lowest set bit is the first such slot met
-                auto probe_group = [&](const u32x4 T) -> u32 {
-                    const u32 mm = (min(T.x ^ n_key, T.x) == 0u ? 1u : 0u) | (min(T.y ^ n_key, T.y) == 0u ? 2u : 0u) |
-                                   (min(T.z ^ n_key, T.z) == 0u ? 4u : 0u) | (min(T.w ^ n_key, T.w) == 0u ? 8u : 0u);
-                    return ((mm * 17u) >> o) & 15u;
-                };
-                u32x4 T = n_tags;
-                u32 g = n_si >> 2;
-                u32 r = probe_group(T);
-                if (r == 0u && !sp_full && sp_act) {                           // home group full of other lines: walk on
-                    for (u32 tries = 1; tries < sp_groups; tries++) {
-                        g = (g + 1u == sp_groups) ? 0u : g + 1u;
-                        T = *reinterpret_cast<const u32x4 *>(sp_tags + 4u * g);
-                        r = probe_group(T);
-                        if (r) break;
-                    }
-                }
-                const u32 idx = (o + (u32)__builtin_ctz(r | 16u)) & 3u;
-                const u32 t = (idx & 2u) ? ((idx & 1u) ? T.w : T.z) : ((idx & 1u) ? T.y : T.x);
-                const u32 si = 4u * g + idx;
+                ZPQ_SP_WALK(sp_tags, sp_groups, n_key, n_si, n_tags, !sp_full && sp_act);
                 if (!sp_act) { }                                               // (wrong copy: nothing to resolve)
                 else if (r == 0u) { status = ZPQ_E_TOOBIG; sp_full = true; }   // every slot taken: the block is larger than promised
                 else if (t == 0u && ++sp_claims > sp_limit) { status = ZPQ_E_TOOBIG; sp_full = true; }   // (nearly) full: stop before probes get long
@@ -675,15 +642,7 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             // first would be waited for as well)
             u32 poff2 = poff, cpo = n_po & ~63u;
             asm volatile("; order: row store after the prefetched rows are consumed" : "+v"(poff2), "+v"(cpo) : "v"(X.r0), "v"(X.r3));
-            if (SPARSE && claim) {
-                const u32x4 z4 = {0, 0, 0, 0};
-                u8 *line = tbase + cpo;
-                sp_tags[claim_si] = n_key;
-                *reinterpret_cast<u32x4 *>(line) = z4;
-                *reinterpret_cast<u32x4 *>(line + 16) = z4;
-                *reinterpret_cast<u32x4 *>(line + 32) = z4;
-                *reinterpret_cast<u32x4 *>(line + 48) = z4;
-            }
+            if (SPARSE && claim) ZPQ_SP_CLAIM(sp_tags, claim_si, n_key, tbase + cpo);
 #ifndef ZPQ_DEBUG_NO_ROWS
             // (one predicate, the lane's part of it computed once: `have_prev && hashed && ...` as written became a twenty-instruction
             //  maze of exec-mask moves around one store)
@@ -700,12 +659,13 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             // program, longer chains = the hash chain): the interpreter and its state exist only in the runtime-loop kernel
             const int vm_kind = NCH == 0 ? cfg.vm_kind : (NCH == 2 ? (int)VM_LEVEL1 : (int)VM_HASHCHAIN);
             if (vm_kind == VM_HASHCHAIN) {
-                // b=c c-- *c=a d=0 (hash *d=a d++)* hash *d=a halt: H[k] = hash^(k+1) of (byte, prev)
+                // the hash chain (zpq_rows.h), every lane keeping the link that is its component's
                 u32 a = byte;
-                for (int k = 0; k < n; k++) { a = (a + prev + 512u) * 773u; hv = (k == lc) ? a : hv; }
+                for (int k = 0; k < n; k++) { a = hash_step(a, prev); hv = (k == lc) ? a : hv; }
                 vm_last = a;
             } else if (vm_kind == VM_LEVEL1) {
-                // *b=a a=0 d=0 hash b-- hash *d=a d++ b-- hash b-- hash *d=a halt, M = 4 bytes
+                // level 1's program, as zpq_rows.h's level1_put / level1_hashes state it -- in place: through them, or with
+                // hash_step alone, the level-1 kernels (and the runtime-loop ones) came out with other code
                 const u32 mm = (m4 & ~(255u << ((b4 & 3) * 8))) | (byte << ((b4 & 3) * 8));
                 u32 bb = b4;
                 u32 a = 0;
@@ -1307,8 +1267,6 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
         auto step = [&](auto kc, auto nbc) {
             if constexpr (HYP) bitstep_hyp(kc, nbc); else bitstep(kc, nbc);
         };
-
-        // nibble start: find_ht (predictor.v:495-532); three rows of one 64-byte line
 
         if constexpr (KEEP) {
             // (h = 0 unless the segment goes on: then what the last byte before the pause left, the MIX2's from its lane)

@@ -31,6 +31,7 @@
 #include "zpq_common.h"
 #include "zpq_chain_cfg.h"
 #include "zpq_dev.h"
+#include "zpq_rows.h"
 #include "zpq_host.h"
 
 namespace zpqd {
@@ -92,11 +93,8 @@ struct StageArgs {
 };
 
 struct Req {             // a request for the three candidate rows of one nibble context, in flight
-    u32x4 A, B, C;
+    Cands c;
     u32 po, chk;
-};
-struct Row {             // a nibble's bit-history row (byte 0 = check) and its tbase offset
-    u32 x, y, z, w, off;
 };
 
 // ------------------------------------------------------------------ a component wave
@@ -145,27 +143,22 @@ __device__ __forceinline__ void dcomp_loop(const StageArgs &S)
     u32 slotn = 1, c8 = 1, yprev = 0;
 
 #ifdef ZPD_DEBUG_NO_ROWS   // timing experiment only (wrong output): no hash-row traffic
-#define ZPD_LOAD_ROWS(q_, po_) do { q_.A = u32x4{(po_), 0, 0, 0}; q_.B = q_.A; q_.C = q_.A; } while (0)
+    constexpr bool NO_ROWS = true;
 #else
-#define ZPD_LOAD_ROWS(q_, po_)                                                          \
-    do {                                                                                \
-        q_.A = *reinterpret_cast<const u32x4 *>(tbase + (po_));                         \
-        q_.B = *reinterpret_cast<const u32x4 *>(tbase + ((po_) ^ 16u));                 \
-        q_.C = *reinterpret_cast<const u32x4 *>(tbase + ((po_) ^ 32u));                 \
-    } while (0)
+    constexpr bool NO_ROWS = false;
 #endif
     // request the three candidate rows of context (hc, c8v) -- h0, h0 ^ 16, h0 ^ 32 of one 64-byte line (predictor.v:495-532)
     auto request = [&](const u32 hc, const u32 c8v) -> Req {
         Req q;
-        const u32 cx = hc + 16u * c8v;
-        q.chk = (cx >> sizebits) & 255u;
-        const u32 h0 = (cx * 16u) & ht_mask;
+        const RowReq rq = row_request(hc, c8v, sizebits, ht_mask);
+        q.chk = rq.chk;
+        const u32 h0 = rq.h0;
         // Inside this kernel a table's 64-byte lines live at their address with bits 6 and 8 exchanged (a bijection; the
         // rows h0 ^ 16, h0 ^ 32 stay inside the line).  The two outcomes of a byte's FOURTH bit lead to contexts 16 apart
         // (predictor.v:558-560), i.e. lines 256 bytes apart: exchanged, the lane pair asks for the two halves of one
         // aligned 128-byte block -- one request to the memory system instead of two (tools/micro/rowlat.hip: -20 % latency).
         q.po = swz ? ((h0 & ~0x140u) | ((h0 >> 2) & 0x40u) | ((h0 << 2) & 0x100u)) : h0;
-        ZPD_LOAD_ROWS(q, q.po);
+        q.c = load_cands<NO_ROWS>(tbase, q.po);
         return q;
     };
     // Resolve hit / victim among the three candidates with selects (find_ht).  L1 = the row of the nibble that is just
@@ -177,47 +170,31 @@ __device__ __forceinline__ void dcomp_loop(const StageArgs &S)
         auto fwd = [](const bool f1, const Row &R1, const u32x4 N) -> u32x4 {
             return u32x4{f1 ? R1.x : N.x, f1 ? R1.y : N.y, f1 ? R1.z : N.z, f1 ? R1.w : N.w};
         };
-        const u32x4 A = fwd(a1, L1, q.A), Bq = fwd(b1, L1, q.B), Cq = fwd(c1, L1, q.C);
+        const u32x4 A = fwd(a1, L1, q.c.A), Bq = fwd(b1, L1, q.c.B), Cq = fwd(c1, L1, q.c.C);
         const u32 chk = q.chk;
-        const bool ma = (A.x & 255u) == chk, mb = (Bq.x & 255u) == chk, mc = (Cq.x & 255u) == chk;
-        const u32 qa = (A.x >> 8) & 255u, qb = (Bq.x >> 8) & 255u, qc = (Cq.x >> 8) & 255u;
-        const bool va = qa <= qb && qa <= qc, vb = qb < qc;             // victim order (predictor.v:513-531)
-        const bool hit = ma || mb || mc;
-        const bool ua = ma || (!hit && va);
-        const bool ub = !ua && (mb || (!hit && vb));
+        ZPQ_ROW_PICK(A.x, Bq.x, Cq.x, chk);
+        // (the take spelled per dword, not find_row's whole-row select: that form compiles to other code here)
         Row R;
-        R.off = ua ? pa : (ub ? pb : pc);
-        const u32 Rx = ua ? A.x : (ub ? Bq.x : Cq.x), Ry = ua ? A.y : (ub ? Bq.y : Cq.y);
-        const u32 Rz = ua ? A.z : (ub ? Bq.z : Cq.z), Rw = ua ? A.w : (ub ? Bq.w : Cq.w);
+        R.off = pick3(ua, ub, pa, pb, pc);
+        const u32 Rx = pick3(ua, ub, A.x, Bq.x, Cq.x), Ry = pick3(ua, ub, A.y, Bq.y, Cq.y);
+        const u32 Rz = pick3(ua, ub, A.z, Bq.z, Cq.z), Rw = pick3(ua, ub, A.w, Bq.w, Cq.w);
         R.x = hit ? Rx : chk; R.y = hit ? Ry : 0u; R.z = hit ? Rz : 0u; R.w = hit ? Rw : 0u;
         return R;
     };
     // ZPAQL.run(byte) + h[] copy (predictor.v:809-816) for the two shipped program shapes -> this component's context;
     // vm_hash does not touch the VM's state (the byte may not be the one decoded), vm_commit does once it is certain
     auto vm_hash = [&](const u32 byte) -> u32 {
-        u32 hv = 0;
         if (NCH != 2) {
-            // b=c c-- *c=a d=0 (hash *d=a d++)* hash *d=a halt: H[k] = hash^(k+1) of (byte, prev)
             u32 a = byte;
-            for (int k = 0; k <= ci; k++) a = (a + prev + 512u) * 773u;
-            hv = a;
-        } else {
-            // level 1: *b=a a=0 d=0 hash b-- hash *d=a d++ b-- hash b-- hash *d=a halt, M = 4 bytes
-            const u32 mm = (m4 & ~(255u << ((b4 & 3) * 8))) | (byte << ((b4 & 3) * 8));
-            u32 bb = b4;
-            u32 a = 0;
-            a = (a + ((mm >> ((bb & 3) * 8)) & 255u) + 512u) * 773u; bb--;
-            a = (a + ((mm >> ((bb & 3) * 8)) & 255u) + 512u) * 773u;
-            const u32 h0v = a; bb--;
-            a = (a + ((mm >> ((bb & 3) * 8)) & 255u) + 512u) * 773u; bb--;
-            a = (a + ((mm >> ((bb & 3) * 8)) & 255u) + 512u) * 773u;
-            hv = (ci == 0) ? h0v : a;
+            for (int k = 0; k <= ci; k++) a = hash_step(a, prev);
+            return a;
         }
-        return hv;
+        const Level1 v = level1_hashes(level1_put(m4, b4, byte), b4);
+        return ci == 0 ? v.h0 : v.h1;
     };
     auto vm_commit = [&](const u32 byte) {
         if (NCH != 2) prev = byte;
-        else { m4 = (m4 & ~(255u << ((b4 & 3) * 8))) | (byte << ((b4 & 3) * 8)); b4 -= 3u; }
+        else { m4 = level1_put(m4, b4, byte); b4 -= 3u; }
     };
 
     Row row = {0, 0, 0, 0, 0xFFFFFFFFu};               // the current nibble's row (both lanes of a block hold it)
@@ -225,7 +202,7 @@ __device__ __forceinline__ void dcomp_loop(const StageArgs &S)
     Req req;
     {
         const u32x4 z4 = {0, 0, 0, 0};
-        req.A = z4; req.B = z4; req.C = z4; req.po = 0; req.chk = 0;
+        req.c = Cands{z4, z4, z4}; req.po = 0; req.chk = 0;
     }
     u32 cur_s = 0, cur_v = 0;                          // the state the bit being decoded is predicted from, its packed entry
     i32 cur_b = 0;
@@ -416,7 +393,6 @@ __device__ __forceinline__ void dcomp_loop(const StageArgs &S)
 #ifdef ZPD_PROF
     prof.flush(ci);
 #endif
-#undef ZPD_LOAD_ROWS
 }
 
 // ------------------------------------------------------------------ the decoder wave (decoder.v:73-145)

@@ -40,6 +40,7 @@
 #include "zpq_host.h"
 #include "zpq_vm.h"
 #include "zpq_dev.h"
+#include "zpq_rows.h"
 
 namespace zpqg {
 
@@ -48,7 +49,6 @@ typedef uint32_t u32;
 typedef uint64_t u64;
 typedef uint8_t u8;
 typedef uint16_t u16;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // vector accesses that are only word-aligned (a MIX row, an SSE pair)
 typedef unsigned int u32x4a __attribute__((ext_vector_type(4), aligned(4)));
 typedef unsigned int u32x3a __attribute__((ext_vector_type(3), aligned(4)));
@@ -253,21 +253,15 @@ __device__ __forceinline__ void comp_stage(const Stage &S)
                         u32 chk[2], h0[2];
 #pragma unroll
                         for (int nb = 0; nb < 2; nb++) {
-                            const u32 cx = hctx + 16u * c8a[4 * nb];
-                            chk[nb] = (cx >> (ca + 2)) & 255u;
-                            h0[nb] = (cx * 16u) & (ht_len - 16u);
+                            const RowReq rq = row_request(hctx, c8a[4 * nb], ca + 2, ht_len - 16u);
+                            chk[nb] = rq.chk; h0[nb] = rq.h0;
                             A[nb] = *reinterpret_cast<const u32x4 *>(ht + h0[nb]);
                             Bq[nb] = *reinterpret_cast<const u32x4 *>(ht + (h0[nb] ^ 16u));
                             Cq[nb] = *reinterpret_cast<const u32x4 *>(ht + (h0[nb] ^ 32u));
                         }
 #pragma unroll
                         for (int nb = 0; nb < 2; nb++) {
-                            const bool ma_ = (A[nb].x & 255u) == chk[nb], mb_ = (Bq[nb].x & 255u) == chk[nb], mc_ = (Cq[nb].x & 255u) == chk[nb];
-                            const u32 qa = (A[nb].x >> 8) & 255u, qb = (Bq[nb].x >> 8) & 255u, qc = (Cq[nb].x >> 8) & 255u;
-                            const bool va = qa <= qb && qa <= qc, vb = qb < qc;
-                            const bool hit = ma_ || mb_ || mc_;
-                            const bool ua = ma_ || (!hit && va);
-                            const bool ub = !ua && (mb_ || (!hit && vb));
+                            ZPQ_ROW_PICK(A[nb].x, Bq[nb].x, Cq[nb].x, chk[nb]);
                             ro[nb] = ua ? h0[nb] : (ub ? (h0[nb] ^ 16u) : (h0[nb] ^ 32u));
                             R[nb][0] = hit ? (ua ? A[nb].x : (ub ? Bq[nb].x : Cq[nb].x)) : chk[nb];
                             R[nb][1] = hit ? (ua ? A[nb].y : (ub ? Bq[nb].y : Cq[nb].y)) : 0u;
@@ -476,18 +470,12 @@ __device__ __forceinline__ void comp_stage(const Stage &S)
                     cm[idx] = (u32)wadd(wadd((i32)pn, upd), count < climit ? 1 : 0);
                 } else if (TYPE == ZT_ICM || TYPE == ZT_ISSE) {  // predictor.v:555-563,615-631,701-709,776-791
                     if (c8 == 1 || (c8 & 0xf0u) == 16u) {        // find_ht (predictor.v:495-532)
-                        const u32 cx = hctx + 16u * c8;
-                        const u32 chk = (cx >> (ca + 2)) & 255u;
-                        const u32 h0 = (cx * 16u) & (ht_len - 16u);
+                        const RowReq rq = row_request(hctx, c8, ca + 2, ht_len - 16u);
+                        const u32 chk = rq.chk, h0 = rq.h0;
                         const u32x4 A = *reinterpret_cast<const u32x4 *>(ht + h0);
                         const u32x4 Bq = *reinterpret_cast<const u32x4 *>(ht + (h0 ^ 16u));
                         const u32x4 Cq = *reinterpret_cast<const u32x4 *>(ht + (h0 ^ 32u));
-                        const bool ma_ = (A.x & 255u) == chk, mb_ = (Bq.x & 255u) == chk, mc_ = (Cq.x & 255u) == chk;
-                        const u32 qa = (A.x >> 8) & 255u, qb = (Bq.x >> 8) & 255u, qc = (Cq.x >> 8) & 255u;
-                        const bool va = qa <= qb && qa <= qc, vb = qb < qc;
-                        const bool hit = ma_ || mb_ || mc_;
-                        const bool ua = ma_ || (!hit && va);
-                        const bool ub = !ua && (mb_ || (!hit && vb));
+                        ZPQ_ROW_PICK(A.x, Bq.x, Cq.x, chk);
                         roff = ua ? h0 : (ub ? (h0 ^ 16u) : (h0 ^ 32u));
                         r0 = hit ? (ua ? A.x : (ub ? Bq.x : Cq.x)) : chk;
                         r1 = hit ? (ua ? A.y : (ub ? Bq.y : Cq.y)) : 0u;
@@ -624,7 +612,7 @@ __device__ __forceinline__ void comp_stage(const Stage &S)
             *ring_at(ci, bi) = make_uint4(out.a, out.b, out.c, out.d);
             if (!VM) {  // ZPAQL.run(byte) of the shipped hash chain: H[ci] for the next byte
                 u32 a = ch;
-                for (u32 k = 0; k < hash_steps; k++) a = (a + prev + 512u) * 773u;
+                for (u32 k = 0; k < hash_steps; k++) a = hash_step(a, prev);
                 hctx = hash_steps ? a : 0u;
                 prev = ch;
             }
@@ -993,18 +981,12 @@ __device__ __forceinline__ void comp_dec(const DStage &S)
                     if (!spec) nx0 = cm[idx];
                 } else if (TYPE == ZT_ICM || TYPE == ZT_ISSE) {
                     if (c8 == 1 || (c8 & 0xf0u) == 16u) {        // find_ht (predictor.v:495-532)
-                        const u32 cx = hctx + 16u * c8;
-                        const u32 chk = (cx >> (ca + 2)) & 255u;
-                        const u32 h0 = (cx * 16u) & (ht_len - 16u);
+                        const RowReq rq = row_request(hctx, c8, ca + 2, ht_len - 16u);
+                        const u32 chk = rq.chk, h0 = rq.h0;
                         const u32x4 A = *reinterpret_cast<const u32x4 *>(ht + h0);
                         const u32x4 Bq = *reinterpret_cast<const u32x4 *>(ht + (h0 ^ 16u));
                         const u32x4 Cq = *reinterpret_cast<const u32x4 *>(ht + (h0 ^ 32u));
-                        const bool ma_ = (A.x & 255u) == chk, mb_ = (Bq.x & 255u) == chk, mc_ = (Cq.x & 255u) == chk;
-                        const u32 qa = (A.x >> 8) & 255u, qb = (Bq.x >> 8) & 255u, qc = (Cq.x >> 8) & 255u;
-                        const bool va = qa <= qb && qa <= qc, vb = qb < qc;
-                        const bool hit = ma_ || mb_ || mc_;
-                        const bool ua = ma_ || (!hit && va);
-                        const bool ub = !ua && (mb_ || (!hit && vb));
+                        ZPQ_ROW_PICK(A.x, Bq.x, Cq.x, chk);
                         roff = ua ? h0 : (ub ? (h0 ^ 16u) : (h0 ^ 32u));
                         r0 = hit ? (ua ? A.x : (ub ? Bq.x : Cq.x)) : chk;
                         r1 = hit ? (ua ? A.y : (ub ? Bq.y : Cq.y)) : 0u;
@@ -1242,7 +1224,7 @@ __device__ __forceinline__ void comp_dec(const DStage &S)
         }
         if (!VM) {
             u32 a = byte;
-            for (u32 k = 0; k < hash_steps; k++) a = (a + prev + 512u) * 773u;
+            for (u32 k = 0; k < hash_steps; k++) a = hash_step(a, prev);
             hctx = hash_steps ? a : 0u;
             if (!KEEP || alive) prev = byte;                     // (a lane whose block has ended sees bits of 0 while its neighbours go on)
         }

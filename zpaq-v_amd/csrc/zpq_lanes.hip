@@ -35,6 +35,7 @@
 #include "zpq_vm.h"
 #include "zpq_host.h"
 #include "zpq_dev.h"
+#include "zpq_rows.h"
 
 namespace zpql {
 
@@ -43,7 +44,6 @@ typedef uint32_t u32;
 typedef uint64_t u64;
 typedef uint8_t u8;
 typedef uint16_t u16;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 using zpqvm::Vm;
 using zpqvm::vm_run;
 using namespace zpqdev;
@@ -93,15 +93,13 @@ __device__ __forceinline__ i32 wave_sum(i32 x)
 }
 
 // SP (k_lanes and k_rows, on request: ZPQ_FLAG_LINESTORE): a hashed component with C.sp_cap != 0 keeps its bit-history rows
-// in the compact line store (zpq_model.cpp zpq_sparse_layout) instead of a dense table, probed as zpq_chain.hip probes it:
-// key = dense line index + 1, home slot = mulhi(key * 0x9E3779B1, cap), tags in groups of four read with one 16-byte load,
-// the home group walked cyclically from the home slot, then the following groups.  find_ht's three candidate rows h0,
-// h0 ^ 16, h0 ^ 32 share one 64-byte line, so one probe per nibble serves them.  Every lane is another component with a
-// store, a claim count and a full flag of its own; dense and compact components meet in one wave.
+// in the compact line store instead of a dense table, addressed and probed as zpq_rows.h says.  find_ht's three candidate
+// rows share one 64-byte line, so one probe per nibble serves them.  Every lane is another component with a store, a claim
+// count and a full flag of its own; dense and compact components meet in one wave.
 // sp_find: the slot of line `key`, given its home slot and the home group's tags T (loaded by the caller together with the
 // home line's rows).  A free slot met first is claimed: its tag is written here, SP_CLAIM tells the caller to zero the line.
-// Past cap - cap/16 claims (the chain kernels' limit), or with every slot taken, the block is refused (ZPQ_E_TOOBIG): the
-// lane walks and claims no more and goes on in the home slot's line -- in bounds, its output unspecified.
+// Past ZPQ_SP_LIMIT claims, or with every slot taken, the block is refused (ZPQ_E_TOOBIG): the lane walks and claims no
+// more and goes on in the home slot's line -- in bounds, its output unspecified.
 // (SP) zpq_dev.h's slot_zero / slot_fill with their loops left rolled: unrolled, every loop keeps first + k * stride in
 // registers across the whole bit loop, which the store forms have no room for (they would spill them)
 __device__ __forceinline__ void slot_zero_rolled(const DModel &M, u8 *slot, const u32 first, const u32 stride)
@@ -140,26 +138,8 @@ constexpr u32 SP_FULL = 0xFFFFFFFFu;                             // claims: the 
 __device__ __forceinline__ u32 sp_find(u32 *tags, const u32 cap, const u32 key, const u32 home, u32x4 T, u32 &claims)
 {
     const bool full = claims == SP_FULL;
-    const u32 o = home & 3u, groups = cap >> 2;
-    // slots of a group that end the probe -- the line's own tag, or a free slot -- as a mask rotated so that bit j stands
-    // for slot (o + j) & 3: the lowest set bit is the first such slot met
-    auto probe_group = [&](const u32x4 t) -> u32 {
-        const u32 mm = (min(t.x ^ key, t.x) == 0u ? 1u : 0u) | (min(t.y ^ key, t.y) == 0u ? 2u : 0u) |
-                       (min(t.z ^ key, t.z) == 0u ? 4u : 0u) | (min(t.w ^ key, t.w) == 0u ? 8u : 0u);
-        return ((mm * 17u) >> o) & 15u;
-    };
-    u32 g = home >> 2, r = probe_group(T);
-    if (r == 0u && !full)
-        for (u32 tries = 1; tries < groups; tries++) {
-            g = (g + 1u == groups) ? 0u : g + 1u;
-            T = *reinterpret_cast<const u32x4 *>(tags + 4u * g);
-            r = probe_group(T);
-            if (r) break;
-        }
-    const u32 idx = (o + (u32)__builtin_ctz(r | 16u)) & 3u;
-    const u32 t = (idx & 2u) ? ((idx & 1u) ? T.w : T.z) : ((idx & 1u) ? T.y : T.x);
-    const u32 si = 4u * g + idx;
-    if (r == 0u || (t == 0u && (full || claims >= cap - (cap >> 4)))) { claims = SP_FULL; return home; }
+    ZPQ_SP_WALK(tags, cap >> 2, key, home, T, !full);
+    if (r == 0u || (t == 0u && (full || claims >= ZPQ_SP_LIMIT(cap)))) { claims = SP_FULL; return home; }
     if (t != 0u) return si;
     claims++;
     tags[si] = key;
@@ -375,25 +355,24 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
                     v0 = cm[(i32)cxt & (i32)(cm_len - 1)];
                 } else if (hashed) {
                     if (nib) {                                   // find_ht (predictor.v:495-532)
-                        const u32 cx = hctx + 16u * c8;
-                        const u32 chk = (cx >> (ca + 2)) & 255u;
-                        const u32 h0 = (cx * 16u) & (ht_len - 16u);
+                        const RowReq rq = row_request(hctx, c8, ca + 2, ht_len - 16u);
+                        const u32 chk = rq.chk, h0 = rq.h0;
                         u8 *pa = ht + h0, *pb = ht + (h0 ^ 16u), *pc = ht + (h0 ^ 32u);
-                        u32 sp_home = 0;
+                        u32 home = 0;
                         if (SP) roff = h0;
                         u32x4 sp_T = {0, 0, 0, 0};
                         u32 *sp_tags = reinterpret_cast<u32 *>(ht - sp_back);
                         if (SP && sp_cap) {                          // the home group's tags and the home line's rows in one round trip
-                            sp_home = __umulhi(((h0 >> 6) + 1u) * 0x9E3779B1u, sp_cap);
-                            sp_T = *reinterpret_cast<const u32x4 *>(sp_tags + (sp_home & ~3u));
-                            const u32 po = (sp_home << 6) + (h0 & 48u);
+                            home = sp_home(sp_key(h0), sp_cap);
+                            sp_T = *reinterpret_cast<const u32x4 *>(sp_tags + (home & ~3u));
+                            const u32 po = (home << 6) + (h0 & 48u);
                             pa = ht + po; pb = ht + (po ^ 16u); pc = ht + (po ^ 32u);
                         }
                         u32x4 A = *reinterpret_cast<const u32x4 *>(pa);
                         u32x4 Bq = *reinterpret_cast<const u32x4 *>(pb);
                         u32x4 Cq = *reinterpret_cast<const u32x4 *>(pc);
                         if (SP && sp_cap) {
-                            const u32 sf = sp_find(sp_tags, sp_cap, (h0 >> 6) + 1u, sp_home, sp_T, sp_claims);
+                            const u32 sf = sp_find(sp_tags, sp_cap, sp_key(h0), home, sp_T, sp_claims);
                             const u32 si = sf & ~SP_CLAIM;
                             const u32 po = (si << 6) + (h0 & 48u);
                             pa = ht + po; pb = ht + (po ^ 16u); pc = ht + (po ^ 32u);
@@ -403,18 +382,13 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
                                 u32x4 *ln = reinterpret_cast<u32x4 *>(ht + (si << 6));
                                 ln[0] = z4; ln[1] = z4; ln[2] = z4; ln[3] = z4;
                                 A = z4; Bq = z4; Cq = z4;
-                            } else if (si != sp_home) {              // displaced when it was claimed: its rows were not the ones fetched
+                            } else if (si != home) {              // displaced when it was claimed: its rows were not the ones fetched
                                 A = *reinterpret_cast<const u32x4 *>(pa);
                                 Bq = *reinterpret_cast<const u32x4 *>(pb);
                                 Cq = *reinterpret_cast<const u32x4 *>(pc);
                             }
                         }
-                        const bool ma_ = (A.x & 255u) == chk, mb_ = (Bq.x & 255u) == chk, mc_ = (Cq.x & 255u) == chk;
-                        const u32 qa = (A.x >> 8) & 255u, qb = (Bq.x >> 8) & 255u, qc = (Cq.x >> 8) & 255u;
-                        const bool va = qa <= qb && qa <= qc, vb = qb < qc;
-                        const bool hit = ma_ || mb_ || mc_;
-                        const bool ua = ma_ || (!hit && va);
-                        const bool ub = !ua && (mb_ || (!hit && vb));
+                        ZPQ_ROW_PICK(A.x, Bq.x, Cq.x, chk);
                         if (SP) roff = ua ? roff : (ub ? roff ^ 16u : roff ^ 32u);   // (SP: the row's offset from ht, dense or compact)
                         else raddr = ua ? pa : (ub ? pb : pc);
                         const u32x4 Rr = ua ? A : (ub ? Bq : Cq);
@@ -673,7 +647,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
                 // H[k] = hash^(k+1)(byte, previous byte), hash: a = (a + *b + 512) * 773 (zpaql.v HASH);
                 // every lane walks the chain and keeps its own link
                 u32 a = byte, hv = 0;
-                for (int k = 0; k < cfg.vm_hashes; k++) { a = (a + vm_prev + 512u) * 773u; hv = (k == lane) ? a : hv; }
+                for (int k = 0; k < cfg.vm_hashes; k++) { a = hash_step(a, vm_prev); hv = (k == lane) ? a : hv; }
                 vm_prev = byte;
                 if (act) hctx = hv;
             } else {
@@ -923,25 +897,24 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
                     v0 = cm[(i32)cxt & (i32)(cm_len - 1)];
                 } else if (hashed) {
                     if (nib) {                                   // find_ht (predictor.v:495-532)
-                        const u32 cx = hctx + 16u * c8;
-                        const u32 chk = (cx >> (ca + 2)) & 255u;
-                        const u32 h0 = (cx * 16u) & (ht_len - 16u);
+                        const RowReq rq = row_request(hctx, c8, ca + 2, ht_len - 16u);
+                        const u32 chk = rq.chk, h0 = rq.h0;
                         u8 *pa = ht + h0, *pb = ht + (h0 ^ 16u), *pc = ht + (h0 ^ 32u);
-                        u32 sp_home = 0;
+                        u32 home = 0;
                         if (SP) roff = h0;
                         u32x4 sp_T = {0, 0, 0, 0};
                         u32 *sp_tags = reinterpret_cast<u32 *>(ht - sp_back);
                         if (SP && sp_cap) {                          // the home group's tags and the home line's rows in one round trip
-                            sp_home = __umulhi(((h0 >> 6) + 1u) * 0x9E3779B1u, sp_cap);
-                            sp_T = *reinterpret_cast<const u32x4 *>(sp_tags + (sp_home & ~3u));
-                            const u32 po = (sp_home << 6) + (h0 & 48u);
+                            home = sp_home(sp_key(h0), sp_cap);
+                            sp_T = *reinterpret_cast<const u32x4 *>(sp_tags + (home & ~3u));
+                            const u32 po = (home << 6) + (h0 & 48u);
                             pa = ht + po; pb = ht + (po ^ 16u); pc = ht + (po ^ 32u);
                         }
                         u32x4 A = *reinterpret_cast<const u32x4 *>(pa);
                         u32x4 Bq = *reinterpret_cast<const u32x4 *>(pb);
                         u32x4 Cq = *reinterpret_cast<const u32x4 *>(pc);
                         if (SP && sp_cap) {
-                            const u32 sf = sp_find(sp_tags, sp_cap, (h0 >> 6) + 1u, sp_home, sp_T, sp_claims);
+                            const u32 sf = sp_find(sp_tags, sp_cap, sp_key(h0), home, sp_T, sp_claims);
                             const u32 si = sf & ~SP_CLAIM;
                             const u32 po = (si << 6) + (h0 & 48u);
                             pa = ht + po; pb = ht + (po ^ 16u); pc = ht + (po ^ 32u);
@@ -951,18 +924,13 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
                                 u32x4 *ln = reinterpret_cast<u32x4 *>(ht + (si << 6));
                                 ln[0] = z4; ln[1] = z4; ln[2] = z4; ln[3] = z4;
                                 A = z4; Bq = z4; Cq = z4;
-                            } else if (si != sp_home) {              // displaced when it was claimed: its rows were not the ones fetched
+                            } else if (si != home) {              // displaced when it was claimed: its rows were not the ones fetched
                                 A = *reinterpret_cast<const u32x4 *>(pa);
                                 Bq = *reinterpret_cast<const u32x4 *>(pb);
                                 Cq = *reinterpret_cast<const u32x4 *>(pc);
                             }
                         }
-                        const bool ma_ = (A.x & 255u) == chk, mb_ = (Bq.x & 255u) == chk, mc_ = (Cq.x & 255u) == chk;
-                        const u32 qa = (A.x >> 8) & 255u, qb = (Bq.x >> 8) & 255u, qc = (Cq.x >> 8) & 255u;
-                        const bool va = qa <= qb && qa <= qc, vb = qb < qc;
-                        const bool hit = ma_ || mb_ || mc_;
-                        const bool ua = ma_ || (!hit && va);
-                        const bool ub = !ua && (mb_ || (!hit && vb));
+                        ZPQ_ROW_PICK(A.x, Bq.x, Cq.x, chk);
                         if (SP) roff = ua ? roff : (ub ? roff ^ 16u : roff ^ 32u);   // (SP: the row's offset from ht, dense or compact)
                         else raddr = ua ? pa : (ub ? pb : pc);
                         u32 *rw = reinterpret_cast<u32 *>(myrow);
@@ -1208,7 +1176,7 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
             const u32 byte = c8 - 256;
             if (VMH) {  // H[k] = hash^(k+1)(byte, previous byte): every lane walks the chain and keeps its own link
                 u32 a = byte, hv = 0;
-                for (int k = 0; k < cfg.vm_hashes; k++) { a = (a + vm_prev + 512u) * 773u; hv = (k == li) ? a : hv; }
+                for (int k = 0; k < cfg.vm_hashes; k++) { a = hash_step(a, vm_prev); hv = (k == li) ? a : hv; }
                 vm_prev = byte;
                 if (act) hctx = hv;
             } else {    // ZPAQL.run(byte); h[i] = z.h[i] (predictor.v:809-816), one interpreter per row

@@ -28,6 +28,7 @@
 #include "zpq_common.h"
 #include "zpq_chain_cfg.h"
 #include "zpq_dev.h"
+#include "zpq_rows.h"
 #include "zpq_host.h"
 
 namespace zpqp {
@@ -114,15 +115,41 @@ struct InWin {
     }
 };
 
+#ifdef ZPP_DEBUG_NO_ROWS   // timing experiment only (wrong output): no hash-row traffic
+constexpr bool NO_ROWS = true;
+#else
+constexpr bool NO_ROWS = false;
+#endif
 // a request for the three candidate rows of one nibble context, in flight
 struct Req {
-    u32x4 A, B, C, tags;
+    Cands c;
+    u32x4 tags;
     u32 po, chk, key, si, off;
 };
 // a nibble's bit-history row (byte 0 = check) and its tbase offset
-struct Row {
-    u32 x, y, z, w, off;
-};
+
+// find_ht on a request's candidates (comp_loop's and hist_loop's consume), taking rows that were finished after the request
+// went out from registers: L1 = the nibble that just ended (not yet stored), L2 (FWD2_) = the one before it (stored after
+// the request was issued).  Forwarding decides on the candidates' FIRST dwords only (check byte and priority live there);
+// the other three dwords are forwarded for the chosen candidate alone: 20 selects per nibble instead of 32 (round 4).
+// Declares Row R (and pa, chk ...) in the consuming lambda, which takes (Req q, have1, L1, have2, L2).
+// (One text for both loops as a macro: as a function it moved instructions in every k_pipe and k_pipe2.)
+#define ZPP_FWD_FIND(FWD2_)                                                                                              \
+    const u32 pa = q.po, pb = q.po ^ 16u, pc = q.po ^ 32u;                                                              \
+    const bool a1 = have1 && pa == L1.off, b1 = have1 && pb == L1.off, c1 = have1 && pc == L1.off;                      \
+    const bool a2 = FWD2_ && have2 && pa == L2.off, b2 = FWD2_ && have2 && pb == L2.off, c2 = FWD2_ && have2 && pc == L2.off; \
+    auto fwd1 = [](const bool f1, const u32 r1, const bool f2, const u32 r2, const u32 n) -> u32 { return f1 ? r1 : (f2 ? r2 : n); }; \
+    const u32 Ax = fwd1(a1, L1.x, a2, L2.x, q.c.A.x), Bx = fwd1(b1, L1.x, b2, L2.x, q.c.B.x), Cx = fwd1(c1, L1.x, c2, L2.x, q.c.C.x); \
+    const u32 chk = q.chk;                                                                                              \
+    ZPQ_ROW_PICK(Ax, Bx, Cx, chk);                                                                                      \
+    Row R;                                                                                                              \
+    R.off = pick3(ua, ub, pa, pb, pc);                                                                                  \
+    const bool g1 = pick3(ua, ub, a1, b1, c1), g2 = pick3(ua, ub, a2, b2, c2);     /* the chosen candidate is a row still in registers */ \
+    const u32 Rx = pick3(ua, ub, Ax, Bx, Cx);                                                                           \
+    const u32 Ry = fwd1(g1, L1.y, g2, L2.y, pick3(ua, ub, q.c.A.y, q.c.B.y, q.c.C.y));                                  \
+    const u32 Rz = fwd1(g1, L1.z, g2, L2.z, pick3(ua, ub, q.c.A.z, q.c.B.z, q.c.C.z));                                  \
+    const u32 Rw = fwd1(g1, L1.w, g2, L2.w, pick3(ua, ub, q.c.A.w, q.c.B.w, q.c.C.w));                                  \
+    R.x = hit ? Rx : chk; R.y = hit ? Ry : 0u; R.z = hit ? Rz : 0u; R.w = hit ? Rw : 0u
 
 // ------------------------------------------------------------------ a component stage
 // IS_LAST: the component the coder follows (its link carries squash(p) and the bit).  FWD_PIN: the last ISSE of a chain
@@ -178,7 +205,7 @@ __device__ __forceinline__ void comp_loop(const StageArgs &S)
     u32 ch = 0;
     bool sp_full = false;
     u32 sp_claims = 0;
-    const u32 sp_limit = sp_cap - (sp_cap >> 4);
+    const u32 sp_limit = ZPQ_SP_LIMIT(sp_cap);
     if constexpr (KEEP) {
         // the hash program's registers, and the store's claim count and full flag, where k_chain<..., KEEP> keeps them
         // (Every stage reads the same two words, and the ICM's wave writes them behind its byte loop: a stage has used its
@@ -192,135 +219,65 @@ __device__ __forceinline__ void comp_loop(const StageArgs &S)
         }
     }
 
-#ifdef ZPP_DEBUG_NO_ROWS   // timing experiment only (wrong output): no hash-row traffic
-#define ZPP_LOAD_ROWS(q_, po_) do { q_.A = u32x4{(po_), 0, 0, 0}; q_.B = q_.A; q_.C = q_.A; } while (0)
-#else
-#define ZPP_LOAD_ROWS(q_, po_)                                                          \
-    do {                                                                                \
-        q_.A = *reinterpret_cast<const u32x4 *>(tbase + (po_));                         \
-        q_.B = *reinterpret_cast<const u32x4 *>(tbase + ((po_) ^ 16u));                 \
-        q_.C = *reinterpret_cast<const u32x4 *>(tbase + ((po_) ^ 32u));                 \
-    } while (0)
-#endif
     // request the three candidate rows of context (hc, c8v) -- h0, h0 ^ 16, h0 ^ 32 of one 64-byte line
-    // (predictor.v:495-532); compact line store as in zpq_chain.hip
+    // (find_ht; SP: with the line store's home group and home slot -- zpq_rows.h)
     auto request = [&](const u32 hc, const u32 c8v) -> Req {
         Req q;
-        const u32 cx = hc + 16u * c8v;
-        q.chk = (cx >> sizebits) & 255u;
-        const u32 h0 = (cx * 16u) & ht_mask;
+        const RowReq rq = row_request(hc, c8v, sizebits, ht_mask);
+        q.chk = rq.chk;
+        const u32 h0 = rq.h0;
         u32 pox = h0;
         q.key = 0; q.si = 0; q.off = 0; q.tags = u32x4{0, 0, 0, 0};
         if (SP && sp_cap) {
-            q.key = (h0 >> 6) + 1u;
-            q.si = __umulhi(q.key * 0x9E3779B1u, sp_cap);
+            q.key = sp_key(h0);
+            q.si = sp_home(q.key, sp_cap);
             q.off = h0 & 48u;
             q.tags = *reinterpret_cast<const u32x4 *>(sp_tags + (q.si & ~3u));
             pox = (q.si << 6) + q.off;
         }
         q.po = pox;
-        ZPP_LOAD_ROWS(q, pox);
+        q.c = load_cands<NO_ROWS>(tbase, pox);
         return q;
     };
-    // Consume a request: resolve hit / victim among the three candidates with selects (find_ht), taking rows that
-    // were finished after the request went out from registers -- L1 = the nibble that just ended (not yet stored),
-    // L2 = the one before it (stored after the request was issued) -- THEN store L1 (vmcnt retires in order: a store
-    // issued before the wait would be waited for as well).
+    // Consume a request: (SP) find the line's slot and claim it if it is new, find_ht with forwarding (ZPP_FWD_FIND), THEN
+    // store L1 (vmcnt retires in order: a store issued before the wait would be waited for as well).
     auto consume = [&](Req q, const bool have1, const Row L1, const bool have2, const Row L2) -> Row {
         bool claim = false;
         u32 claim_si = 0;
         if (SP && sp_cap) {
-            const u32 o = q.si & 3u;
-            auto probe_group = [&](const u32x4 T) -> u32 {
-                const u32 mm = (min(T.x ^ q.key, T.x) == 0u ? 1u : 0u) | (min(T.y ^ q.key, T.y) == 0u ? 2u : 0u) |
-                               (min(T.z ^ q.key, T.z) == 0u ? 4u : 0u) | (min(T.w ^ q.key, T.w) == 0u ? 8u : 0u);
-                return ((mm * 17u) >> o) & 15u;
-            };
-            u32x4 T = q.tags;
-            u32 g = q.si >> 2;
-            u32 r = probe_group(T);
-            if (r == 0u && !sp_full) {
-                for (u32 tries = 1; tries < sp_groups; tries++) {
-                    g = (g + 1u == sp_groups) ? 0u : g + 1u;
-                    T = *reinterpret_cast<const u32x4 *>(sp_tags + 4u * g);
-                    r = probe_group(T);
-                    if (r) break;
-                }
-            }
-            const u32 idx = (o + (u32)__builtin_ctz(r | 16u)) & 3u;
-            const u32 t = (idx & 2u) ? ((idx & 1u) ? T.w : T.z) : ((idx & 1u) ? T.y : T.x);
-            const u32 si = 4u * g + idx;
+            ZPQ_SP_WALK(sp_tags, sp_groups, q.key, q.si, q.tags, !sp_full);
             if (r == 0u) { status = ZPQ_E_TOOBIG; sp_full = true; }
             else if (t == 0u && ++sp_claims > sp_limit) { status = ZPQ_E_TOOBIG; sp_full = true; }
             else if (t == 0u) {
                 const u32x4 z4 = {0, 0, 0, 0};
                 claim = true;
                 claim_si = si;
-                q.A = z4; q.B = z4; q.C = z4;
+                q.c.A = z4; q.c.B = z4; q.c.C = z4;
                 q.po = (si << 6) + q.off;
             } else if (si != q.si) {
                 q.po = (si << 6) + q.off;
-                ZPP_LOAD_ROWS(q, q.po);
+                q.c = load_cands<NO_ROWS>(tbase, q.po);
             }
         }
-        const u32 pa = q.po, pb = q.po ^ 16u, pc = q.po ^ 32u;
-        const bool a1 = have1 && pa == L1.off, b1 = have1 && pb == L1.off, c1 = have1 && pc == L1.off;
-        const bool a2 = FWD2 && have2 && pa == L2.off, b2 = FWD2 && have2 && pb == L2.off, c2 = FWD2 && have2 && pc == L2.off;
-        // Forwarding decides on the candidates' FIRST dwords only (check byte and priority live there); the other three dwords
-        // are forwarded for the chosen candidate alone: 20 selects per nibble instead of 32 (round 4).
-        auto fwd1 = [](const bool f1, const u32 r1, const bool f2, const u32 r2, const u32 n) -> u32 { return f1 ? r1 : (f2 ? r2 : n); };
-        const u32 Ax = fwd1(a1, L1.x, a2, L2.x, q.A.x), Bx = fwd1(b1, L1.x, b2, L2.x, q.B.x), Cx = fwd1(c1, L1.x, c2, L2.x, q.C.x);
-        const u32 chk = q.chk;
-        const bool ma = (Ax & 255u) == chk, mb = (Bx & 255u) == chk, mc = (Cx & 255u) == chk;
-        const u32 qa = (Ax >> 8) & 255u, qb = (Bx >> 8) & 255u, qc = (Cx >> 8) & 255u;
-        const bool va = qa <= qb && qa <= qc, vb = qb < qc;             // victim order (predictor.v:513-531)
-        const bool hit = ma || mb || mc;
-        const bool ua = ma || (!hit && va);
-        const bool ub = !ua && (mb || (!hit && vb));
-        Row R;
-        R.off = ua ? pa : (ub ? pb : pc);
-        const bool g1 = ua ? a1 : (ub ? b1 : c1), g2 = ua ? a2 : (ub ? b2 : c2);     // the chosen candidate is a row still in registers
-        const u32 Rx = ua ? Ax : (ub ? Bx : Cx);
-        const u32 Ry = fwd1(g1, L1.y, g2, L2.y, ua ? q.A.y : (ub ? q.B.y : q.C.y));
-        const u32 Rz = fwd1(g1, L1.z, g2, L2.z, ua ? q.A.z : (ub ? q.B.z : q.C.z));
-        const u32 Rw = fwd1(g1, L1.w, g2, L2.w, ua ? q.A.w : (ub ? q.B.w : q.C.w));
-        R.x = hit ? Rx : chk; R.y = hit ? Ry : 0u; R.z = hit ? Rz : 0u; R.w = hit ? Rw : 0u;
+        ZPP_FWD_FIND(FWD2);
         u32 poff2 = L1.off, cpo = q.po & ~63u;
         asm volatile("; order: row store after the prefetched rows are consumed" : "+v"(poff2), "+v"(cpo) : "v"(R.x), "v"(R.w));
-        if (SP && claim) {
-            const u32x4 z4 = {0, 0, 0, 0};
-            u8 *line = tbase + cpo;
-            sp_tags[claim_si] = q.key;
-            *reinterpret_cast<u32x4 *>(line) = z4;
-            *reinterpret_cast<u32x4 *>(line + 16) = z4;
-            *reinterpret_cast<u32x4 *>(line + 32) = z4;
-            *reinterpret_cast<u32x4 *>(line + 48) = z4;
-        }
-#ifndef ZPP_DEBUG_NO_ROWS
-        if (have1) *reinterpret_cast<u32x4 *>(tbase + poff2) = u32x4{L1.x, L1.y, L1.z, L1.w};
-#endif
+        if (SP && claim) ZPQ_SP_CLAIM(sp_tags, claim_si, q.key, tbase + cpo);
+        if (!NO_ROWS && have1) *reinterpret_cast<u32x4 *>(tbase + poff2) = u32x4{L1.x, L1.y, L1.z, L1.w};
         return R;
     };
-    // ZPAQL.run(byte) + h[] copy (predictor.v:809-816) for the two shipped program shapes -> this component's context
+    // the shipped program shape's context for this component (zpq_rows.h: the hash chain, level 1's program)
     auto run_vm = [&](const u32 byte) -> u32 {
         u32 hv = 0;
         if (NCH != 2) {
-            // b=c c-- *c=a d=0 (hash *d=a d++)* hash *d=a halt: H[k] = hash^(k+1) of (byte, prev)
             u32 a = byte;
-            for (int k = 0; k <= ci; k++) a = (a + prev + 512u) * 773u;
+            for (int k = 0; k <= ci; k++) a = hash_step(a, prev);
             hv = a;
             prev = byte;
         } else {
-            // level 1: *b=a a=0 d=0 hash b-- hash *d=a d++ b-- hash b-- hash *d=a halt, M = 4 bytes
-            m4 = (m4 & ~(255u << ((b4 & 3) * 8))) | (byte << ((b4 & 3) * 8));
-            u32 bb = b4;
-            u32 a = 0;
-            a = (a + ((m4 >> ((bb & 3) * 8)) & 255u) + 512u) * 773u; bb--;
-            a = (a + ((m4 >> ((bb & 3) * 8)) & 255u) + 512u) * 773u;
-            const u32 h0v = a; bb--;
-            a = (a + ((m4 >> ((bb & 3) * 8)) & 255u) + 512u) * 773u; bb--;
-            a = (a + ((m4 >> ((bb & 3) * 8)) & 255u) + 512u) * 773u;
-            hv = (ci == 0) ? h0v : a;
+            m4 = level1_put(m4, b4, byte);
+            const Level1 v = level1_hashes(m4, b4);
+            hv = (ci == 0) ? v.h0 : v.h1;
             b4 -= 3u;
         }
         return hv;
@@ -420,7 +377,7 @@ __device__ __forceinline__ void comp_loop(const StageArgs &S)
     Req reqX, reqY;                                    // in flight: a first-nibble context, a second-nibble context
     {
         const u32x4 z4 = {0, 0, 0, 0};
-        reqX.A = z4; reqX.B = z4; reqX.C = z4; reqX.tags = z4; reqX.po = 0; reqX.chk = 0; reqX.key = 0; reqX.si = 0; reqX.off = 0;
+        reqX.c = Cands{z4, z4, z4}; reqX.tags = z4; reqX.po = 0; reqX.chk = 0; reqX.key = 0; reqX.si = 0; reqX.off = 0;
         reqY = reqX;
     }
     if (S.active && total) {
@@ -495,7 +452,6 @@ __device__ __forceinline__ void comp_loop(const StageArgs &S)
         }
     }
     if (S.lane < S.bpw) reinterpret_cast<i32 *>(lds + S.L.stat_off)[ci * S.bpw + S.lane] = status;
-#undef ZPP_LOAD_ROWS
 }
 
 // ------------------------------------------------------------------ a component's stage SPLIT in two (levels 1-2)
@@ -528,73 +484,34 @@ __device__ __forceinline__ void hist_loop(const StageArgs &S, const int delay)
     u32 prev = 0, m4 = 0, b4 = 0;
     u32 slotn = 1;
     u32 ch = 0;
-#ifdef ZPP_DEBUG_NO_ROWS   // timing experiment only (wrong output): no hash-row traffic
-#define ZPH_LOAD_ROWS(q_, po_) do { q_.A = u32x4{(po_), 0, 0, 0}; q_.B = q_.A; q_.C = q_.A; } while (0)
-#else
-#define ZPH_LOAD_ROWS(q_, po_)                                                          \
-    do {                                                                                \
-        q_.A = *reinterpret_cast<const u32x4 *>(tbase + (po_));                         \
-        q_.B = *reinterpret_cast<const u32x4 *>(tbase + ((po_) ^ 16u));                 \
-        q_.C = *reinterpret_cast<const u32x4 *>(tbase + ((po_) ^ 32u));                 \
-    } while (0)
-#endif
     auto request = [&](const u32 hc, const u32 c8v) -> Req {
         Req q;
-        const u32 cx = hc + 16u * c8v;
-        q.chk = (cx >> sizebits) & 255u;
-        q.po = (cx * 16u) & ht_mask;
+        const RowReq rq = row_request(hc, c8v, sizebits, ht_mask);
+        q.chk = rq.chk;
+        q.po = rq.h0;
         q.key = 0; q.si = 0; q.off = 0; q.tags = u32x4{0, 0, 0, 0};
-        ZPH_LOAD_ROWS(q, q.po);
+        q.c = load_cands<NO_ROWS>(tbase, q.po);
         return q;
     };
-    // find_ht with the rows of the two nibbles finished since the request went out taken from registers (comp_loop, FWD2)
+    // comp_loop's consume on a dense table, always at the two-nibble distance: no probe, no claim
     auto consume = [&](Req q, const bool have1, const Row L1, const bool have2, const Row L2) -> Row {
-        const u32 pa = q.po, pb = q.po ^ 16u, pc = q.po ^ 32u;
-        const bool a1 = have1 && pa == L1.off, b1 = have1 && pb == L1.off, c1 = have1 && pc == L1.off;
-        const bool a2 = have2 && pa == L2.off, b2 = have2 && pb == L2.off, c2 = have2 && pc == L2.off;
-        // Forwarding decides on the candidates' FIRST dwords only (check byte and priority live there); the other three dwords
-        // are forwarded for the chosen candidate alone: 20 selects per nibble instead of 32 (round 4).
-        auto fwd1 = [](const bool f1, const u32 r1, const bool f2, const u32 r2, const u32 n) -> u32 { return f1 ? r1 : (f2 ? r2 : n); };
-        const u32 Ax = fwd1(a1, L1.x, a2, L2.x, q.A.x), Bx = fwd1(b1, L1.x, b2, L2.x, q.B.x), Cx = fwd1(c1, L1.x, c2, L2.x, q.C.x);
-        const u32 chk = q.chk;
-        const bool ma = (Ax & 255u) == chk, mb = (Bx & 255u) == chk, mc = (Cx & 255u) == chk;
-        const u32 qa = (Ax >> 8) & 255u, qb = (Bx >> 8) & 255u, qc = (Cx >> 8) & 255u;
-        const bool va = qa <= qb && qa <= qc, vb = qb < qc;             // victim order (predictor.v:513-531)
-        const bool hit = ma || mb || mc;
-        const bool ua = ma || (!hit && va);
-        const bool ub = !ua && (mb || (!hit && vb));
-        Row R;
-        R.off = ua ? pa : (ub ? pb : pc);
-        const bool g1 = ua ? a1 : (ub ? b1 : c1), g2 = ua ? a2 : (ub ? b2 : c2);     // the chosen candidate is a row still in registers
-        const u32 Rx = ua ? Ax : (ub ? Bx : Cx);
-        const u32 Ry = fwd1(g1, L1.y, g2, L2.y, ua ? q.A.y : (ub ? q.B.y : q.C.y));
-        const u32 Rz = fwd1(g1, L1.z, g2, L2.z, ua ? q.A.z : (ub ? q.B.z : q.C.z));
-        const u32 Rw = fwd1(g1, L1.w, g2, L2.w, ua ? q.A.w : (ub ? q.B.w : q.C.w));
-        R.x = hit ? Rx : chk; R.y = hit ? Ry : 0u; R.z = hit ? Rz : 0u; R.w = hit ? Rw : 0u;
+        ZPP_FWD_FIND(true);
         u32 poff2 = L1.off;
         asm volatile("; order: row store after the prefetched rows are consumed" : "+v"(poff2) : "v"(R.x), "v"(R.w));
-#ifndef ZPP_DEBUG_NO_ROWS
-        if (have1) *reinterpret_cast<u32x4 *>(tbase + poff2) = u32x4{L1.x, L1.y, L1.z, L1.w};
-#endif
+        if (!NO_ROWS && have1) *reinterpret_cast<u32x4 *>(tbase + poff2) = u32x4{L1.x, L1.y, L1.z, L1.w};
         return R;
     };
     auto run_vm = [&](const u32 byte) -> u32 {         // comp_loop
         u32 hv = 0;
         if (NCH != 2) {
             u32 a = byte;
-            for (int k = 0; k <= ci; k++) a = (a + prev + 512u) * 773u;
+            for (int k = 0; k <= ci; k++) a = hash_step(a, prev);
             hv = a;
             prev = byte;
         } else {
-            m4 = (m4 & ~(255u << ((b4 & 3) * 8))) | (byte << ((b4 & 3) * 8));
-            u32 bb = b4;
-            u32 a = 0;
-            a = (a + ((m4 >> ((bb & 3) * 8)) & 255u) + 512u) * 773u; bb--;
-            a = (a + ((m4 >> ((bb & 3) * 8)) & 255u) + 512u) * 773u;
-            const u32 h0v = a; bb--;
-            a = (a + ((m4 >> ((bb & 3) * 8)) & 255u) + 512u) * 773u; bb--;
-            a = (a + ((m4 >> ((bb & 3) * 8)) & 255u) + 512u) * 773u;
-            hv = (ci == 0) ? h0v : a;
+            m4 = level1_put(m4, b4, byte);
+            const Level1 v = level1_hashes(m4, b4);
+            hv = (ci == 0) ? v.h0 : v.h1;
             b4 -= 3u;
         }
         return hv;
@@ -639,7 +556,7 @@ __device__ __forceinline__ void hist_loop(const StageArgs &S, const int delay)
     Req reqX, reqY;
     {
         const u32x4 z4 = {0, 0, 0, 0};
-        reqX.A = z4; reqX.B = z4; reqX.C = z4; reqX.tags = z4; reqX.po = 0; reqX.chk = 0; reqX.key = 0; reqX.si = 0; reqX.off = 0;
+        reqX.c = Cands{z4, z4, z4}; reqX.tags = z4; reqX.po = 0; reqX.chk = 0; reqX.key = 0; reqX.si = 0; reqX.off = 0;
         reqY = reqX;
     }
     if (S.active && total) {
@@ -681,7 +598,6 @@ __device__ __forceinline__ void hist_loop(const StageArgs &S, const int delay)
     if (HIO && phase == 0 && B.gate_flag && !gate_wait(B.gate_flag)) status = ZPQ_E_INTERNAL;
     }   // phase
     if (S.lane < S.bpw) reinterpret_cast<i32 *>(lds + S.L.stat_off)[ci * S.bpw + S.lane] = status;
-#undef ZPH_LOAD_ROWS
 }
 
 // the counter / weights half of a stage (see hist_loop): states from its history wave, an ISSE's inputs from its predecessor
@@ -843,7 +759,7 @@ __device__ __forceinline__ void mix_loop(const StageArgs &S)
             u32 hnext;
             {   // H[NCH] = hash^(NCH+1)(byte, previous byte)
                 u32 a = ch;
-                for (int k = 0; k <= NCH; k++) a = (a + prev + 512u) * 773u;
+                for (int k = 0; k <= NCH; k++) a = hash_step(a, prev);
                 hnext = a;
                 prev = ch;
             }
