@@ -378,6 +378,13 @@ int zpq_block_decode_segment(zpq_block *, const uint8_t *in, size_t n, uint32_t 
  *                         1-16 times per byte (zpaql_programs "loop_count") it LOSES at every member count measured, 16
  *                         included (encode 7-37 %, decode 16-51 % slower): one wave runs the 64 members' interpreters in
  *                         lockstep, k_rows one interpreter per row of lanes.  Leave such sets on ZPQ_SET_LANES alone.
+ *   ZPQ_SET_CHUNKS        a request on top of ZPQ_SET_LANES: let zpq_blockset_{encode,decode}_chunks (below) code such a set, on
+ *                         k_rows / k_lanes -- without it they return ZPQ_E_ARG for a ZPQ_SET_LANES set, as they always have.
+ *                         Honoured where ZPQ_SET_LANES is in force for the set (flag or environment, and honoured); anywhere
+ *                         else it decides nothing: a chain-model set or a plain set resolves as without it and chunks as
+ *                         without it.  A honoured set reports 129, 145 (| ZPQ_SET_WAVES) or 193 (| ZPQ_SET_VMWAVES).  It has no
+ *                         environment variable -- nothing in a process but a caller of the chunk calls can use it -- and
+ *                         changes neither the capacity nor the whole-segment calls of the set.  The value is 128.
  *   zpq_blockset_flags    the ZPQ_SET_* in force for a set (0 for a request that decided nothing).  Like every call on a
  *                         set it must not race with zpq_blockset_destroy of the same handle.
  *   zpq_blockset_lanes_applies / _pipe_applies / _waves_applies / _vmwaves_applies / zpq_blockset_resolve_flags   host logic only, no device
@@ -388,6 +395,7 @@ int zpq_block_decode_segment(zpq_block *, const uint8_t *in, size_t n, uint32_t 
 #define ZPQ_SET_PIPE 4u
 #define ZPQ_SET_WAVES 16u
 #define ZPQ_SET_VMWAVES 64u
+#define ZPQ_SET_CHUNKS 128u
 typedef struct zpq_blockset zpq_blockset;
 int zpq_blockset_create(zpq_ctx *, const zpq_model *, int nmembers, uint64_t max_member_bytes, zpq_blockset **out);
 int zpq_blockset_create_ex(zpq_ctx *, const zpq_model *, int nmembers, uint64_t max_member_bytes, uint32_t flags, zpq_blockset **out);
@@ -436,9 +444,14 @@ int zpq_blockset_decode_segments(zpq_blockset *, int n, const int32_t *member, c
  * return ZPQ_E_ARG with nothing coded; ZPQ_FLAG_NOEOF stays ZPQ_E_ARG; a failed member is never open.
  * Kernels: chain models on k_chain<..., KEEP> in both directions -- on a ZPQ_SET_PIPE set too, every encode_chunks call runs on
  * "k_chain<encode>" (same slot format, as for that flag's per-call choice) --, every other model on the lane-0 kernel, a launch
- * per member.  A set on which ZPQ_SET_LANES is in force (flags 1, 17, 65) returns ZPQ_E_ARG from both chunk calls: carrying
- * the pause to k_rows / k_lanes / k_wset / k_vset is later work, as are zpq_block_* and the archive layer / front end (which
- * still re-decode with a larger slab).
+ * per member.  A set on which ZPQ_SET_LANES is in force returns ZPQ_E_ARG from both chunk calls (flags 1, 17, 65) unless it was
+ * created with ZPQ_SET_CHUNKS (129, 145, 193): then every chunk call is ONE launch of k_rows / k_lanes<..., KEEP>
+ * ("k_rows<encode>" ..., ZPQ_LANES_ROWS choosing between the two per call: they read each other's pauses), on a 145 or 193 set
+ * too -- its chunk calls never run on k_wset / k_vset, as a ZPQ_SET_PIPE set's never run on k_pipe, while its whole-segment
+ * calls go on choosing per call (one slot format).  Measured on C4b (profiles/r22_set_lanes_chunks.txt): a chunk call of 256 bytes
+ * takes 42x (16 members) to 630x (256 members) less wall-clock time than on a plain set's lane-0 kernel, 16 chunk calls cost 1.00-1.01x
+ * the kernel time of one call, and a set that never chunks pays nothing for the pause.  Carrying the pause to k_wset / k_wsetd / k_vset / k_vsetd and to KEEP forms on the
+ * line store is later work, as are zpq_block_* and the archive layer / front end (which still re-decode with a larger slab).
  */
 int zpq_blockset_encode_chunks(zpq_blockset *, int n, const int32_t *member, const uint8_t *in, const uint64_t *in_off,
                                uint32_t flags, const uint8_t *more /* n entries, NULL = all 0 */,

@@ -21,6 +21,7 @@ SET_LANES = 1                                # zpq_blockset_create_ex / zpq_bloc
 SET_PIPE = 4
 SET_WAVES = 16
 SET_VMWAVES = 64
+SET_CHUNKS = 128
 _LIB = None
 # Handle lifetime on the Python side (the C side tolerates any destroy order as well, include/zpaq_hip.h): every live
 # Context, Block and PinnedArray is tracked; Context.close() closes its blocks first; at interpreter exit everything
@@ -501,9 +502,9 @@ class Block:
         return out.raw[:olen.value], cons.value, code.value, first.value
 
 
-def _set_flags(lanes, pipe, waves, vmwaves=False):
-    return ((SET_LANES if lanes or waves or vmwaves else 0) | (SET_PIPE if pipe else 0) | (SET_WAVES if waves else 0)
-            | (SET_VMWAVES if vmwaves else 0))
+def _set_flags(lanes, pipe, waves, vmwaves=False, chunks=False):
+    return ((SET_LANES if lanes or waves or vmwaves or chunks else 0) | (SET_PIPE if pipe else 0) | (SET_WAVES if waves else 0)
+            | (SET_VMWAVES if vmwaves else 0) | (SET_CHUNKS if chunks else 0))
 
 
 class BlockSet:
@@ -516,18 +517,21 @@ class BlockSet:
     waves=True requests, with lanes, the wave-per-component kernels (ZPQ_SET_LANES | ZPQ_SET_WAVES: k_wset / k_wsetd for a
     model both take; same coded bytes); read-only `waves` likewise.  vmwaves=True requests, with lanes, the same for a
     model whose HCOMP program is not the shipped hash chain (ZPQ_SET_LANES | ZPQ_SET_VMWAVES: k_vset / k_vsetd, with a wave
-    that runs the ZPAQL interpreter; same coded bytes); read-only `vmwaves` likewise.  No model gets both."""
+    that runs the ZPAQL interpreter; same coded bytes); read-only `vmwaves` likewise.  No model gets both.  chunks=True requests,
+    with lanes, that encode_chunks / decode_chunks code such a set, on k_rows / k_lanes (ZPQ_SET_LANES | ZPQ_SET_CHUNKS; without
+    it they raise ZPQ_E_ARG on a lanes set); read-only `chunks` likewise."""
 
-    def __init__(self, ctx, model, nmembers, max_member_bytes=0, lanes=False, pipe=False, waves=False, vmwaves=False):
+    def __init__(self, ctx, model, nmembers, max_member_bytes=0, lanes=False, pipe=False, waves=False, vmwaves=False, chunks=False):
         self.ctx, self.model, self.nmembers = ctx, model, nmembers
         self.h = C.c_void_p()
         _ck(lib().zpq_blockset_create_ex(ctx.h, model.h, nmembers, max_member_bytes,
-                                         _set_flags(lanes, pipe, waves, vmwaves), C.byref(self.h)),
+                                         _set_flags(lanes, pipe, waves, vmwaves, chunks), C.byref(self.h)),
             "zpq_blockset_create")
         self._lanes = bool(lib().zpq_blockset_flags(self.h) & SET_LANES)
         self._pipe = bool(lib().zpq_blockset_flags(self.h) & SET_PIPE)
         self._waves = bool(lib().zpq_blockset_flags(self.h) & SET_WAVES)
         self._vmwaves = bool(lib().zpq_blockset_flags(self.h) & SET_VMWAVES)
+        self._chunks = bool(lib().zpq_blockset_flags(self.h) & SET_CHUNKS)
         ctx._children.add(self)
 
     @property
@@ -545,6 +549,10 @@ class BlockSet:
     @property
     def vmwaves(self):
         return self._vmwaves
+
+    @property
+    def chunks(self):
+        return self._chunks
 
     def close(self):
         if getattr(self, "h", None) and _LIB is not None:

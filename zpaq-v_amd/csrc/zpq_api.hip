@@ -29,7 +29,7 @@
 #include "zpq_common.h"
 #include "zpq_host.h"
 
-#define ZPQ_SET_ALL (ZPQ_SET_LANES | ZPQ_SET_PIPE | ZPQ_SET_WAVES | ZPQ_SET_VMWAVES)
+#define ZPQ_SET_ALL (ZPQ_SET_LANES | ZPQ_SET_PIPE | ZPQ_SET_WAVES | ZPQ_SET_VMWAVES | ZPQ_SET_CHUNKS)
 
 #define HIPCK(x)                                                              \
     do {                                                                      \
@@ -1349,7 +1349,11 @@ extern "C" int zpq_blockset_resolve_flags(const zpq_model *m, uint32_t flags) tr
     const bool pipe = request("ZPQ_SET_PIPE", flags, ZPQ_SET_PIPE) && zpq_blockset_pipe_applies(m);
     const bool waves = lanes && request("ZPQ_SET_WAVES", flags, ZPQ_SET_WAVES) && zpq_blockset_waves_applies(m);
     const bool vmwaves = lanes && request("ZPQ_SET_VMWAVES", flags, ZPQ_SET_VMWAVES) && zpq_blockset_vmwaves_applies(m);
-    return (int)((lanes ? ZPQ_SET_LANES : 0u) | (pipe ? ZPQ_SET_PIPE : 0u) | (waves ? ZPQ_SET_WAVES : 0u) | (vmwaves ? ZPQ_SET_VMWAVES : 0u));
+    // ZPQ_SET_CHUNKS, a request on top of ZPQ_SET_LANES with no environment variable (only a caller of the chunk calls can use
+    // it): honoured wherever that one is in force, it decides nothing anywhere else
+    const bool chunks = lanes && (flags & ZPQ_SET_CHUNKS) != 0;
+    return (int)((lanes ? ZPQ_SET_LANES : 0u) | (pipe ? ZPQ_SET_PIPE : 0u) | (waves ? ZPQ_SET_WAVES : 0u) | (vmwaves ? ZPQ_SET_VMWAVES : 0u)
+                 | (chunks ? ZPQ_SET_CHUNKS : 0u));
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 static int set_capacity(zpq_ctx *c, const DModel &layout, bool chain, bool lanes)
@@ -1490,7 +1494,9 @@ static int set_segments(zpq_blockset *s, int decode, const int32_t *member, cons
             mem[(size_t)i] = k;
         }
     }
-    if (chunk && ((s->flags & ZPQ_SET_LANES) || s->layout.n < 1 || (decode && !open_out))) return ZPQ_E_ARG;
+    // (a ZPQ_SET_LANES set takes chunk calls only where ZPQ_SET_CHUNKS was asked for at its creation)
+    const bool lane_chunks = chunk && (s->flags & ZPQ_SET_CHUNKS) != 0;
+    if (chunk && (((s->flags & ZPQ_SET_LANES) && !lane_chunks) || s->layout.n < 1 || (decode && !open_out))) return ZPQ_E_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     // an open segment belongs to the chunk calls of the direction that opened it
     for (int i = 0; i < n; i++) {
@@ -1533,7 +1539,7 @@ static int set_segments(zpq_blockset *s, int decode, const int32_t *member, cons
         h_in[j + 1] = h_in[j] + (h.in_off[i + 1] - h.in_off[i]);
         h_out[j + 1] = h_out[j] + (h.out_off[i + 1] - h.out_off[i]);
         h_map[(size_t)j] = mem[(size_t)i];
-        if (chunk && s->chain)   // (k_chain<..., KEEP> alone reads these marks: chunk calls never run on k_pipe)
+        if (chunk && (s->chain || lane_chunks))   // (k_chain / k_rows / k_lanes<..., KEEP> alone read these marks: chunk calls never run on k_pipe, k_wset, k_vset)
             h_map[(size_t)j] |= (s->open[(size_t)mem[(size_t)i]] ? ZB_MAP_CONT : 0) | (!decode && more && more[i] ? ZB_MAP_MORE : 0);
     }
     if (all) { if (in_bytes) HIPCK(hipMemcpyAsync(S.in.p, h.in + h.in_off[0], (size_t)in_bytes, hipMemcpyHostToDevice, st)); }
@@ -1549,7 +1555,7 @@ static int set_segments(zpq_blockset *s, int decode, const int32_t *member, cons
         DevModel dm;
         if ((rc = get_dev_model(c, s->model, s->layout, s->sp, &dm)) != ZPQ_OK) return rc;
         dv.flags = (dv.flags & ~(uint32_t)(ZPQ_FLAG_GENERIC | ZPQ_FLAG_LANES)) | ZB_KEEP_STATE;
-        if (chunk) dv.flags |= ZB_CHUNK;                                            // (always k_chain<..., KEEP>, ZPQ_SET_PIPE or not)
+        if (chunk) dv.flags |= ZB_CHUNK;   // (always k_chain<..., KEEP>, ZPQ_SET_PIPE or not; always k_rows / k_lanes<..., KEEP>, ZPQ_SET_WAVES / _VMWAVES or not)
         else if (!decode && (s->flags & ZPQ_SET_PIPE)) dv.flags |= ZB_SET_PIPE;   // this call may run on k_pipe<..., KEEP> (zpq_launch_chain)
         DBatch B = batch_base(c, dm, dv);
         B.slots = s->slots; B.nslots = k;
@@ -1570,7 +1576,8 @@ static int set_segments(zpq_blockset *s, int decode, const int32_t *member, cons
             // (the KEEP launchers are not a batch call's families: they have no row in FAMILY)
             const char *ev = getenv(decode ? "ZPQ_DEC_GPIPE" : "ZPQ_ENC_GPIPE");
             const bool on = !(ev && atoi(ev) == 0);
-            const bool waves = (s->flags & ZPQ_SET_WAVES) != 0 && on, vmwaves = (s->flags & ZPQ_SET_VMWAVES) != 0 && on;
+            // A chunk call (ZPQ_SET_CHUNKS) always runs on k_rows / k_lanes: the pause is theirs alone.
+            const bool waves = (s->flags & ZPQ_SET_WAVES) != 0 && on && !chunk, vmwaves = (s->flags & ZPQ_SET_VMWAVES) != 0 && on && !chunk;
             rc = timed_launch(c, st, [&](const char **name) {
                 if (waves || vmwaves) return (waves ? zpq_launch_wset : zpq_launch_vset)(&B, &s->layout, decode, st, name);
                 *name = zpq_lanes_kernel_name(&s->layout, decode);
@@ -1599,7 +1606,7 @@ static int set_segments(zpq_blockset *s, int decode, const int32_t *member, cons
     deliver(S, h, decode, live.data());
     for (int j = 0; j < k; j++) {
         const int i = live[(size_t)j];
-        const int32_t mb = h_map[(size_t)j] & ZB_MAP_SLOT;              // (a chunk call on a chain set: the entry carries ZB_MAP_* as well)
+        const int32_t mb = h_map[(size_t)j] & ZB_MAP_SLOT;              // (a chunk call on a chain or ZPQ_SET_CHUNKS set: the entry carries ZB_MAP_* as well)
         s->fresh[(size_t)mb] = 0;
         // still open: an encoder that was told so; a decoder that says it paused, its slab full, in front of the next EOF flag
         // (ZB_ST_PAUSED, which stays in here).  A failed member is never open.

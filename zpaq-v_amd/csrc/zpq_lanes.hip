@@ -49,6 +49,7 @@ using zpqvm::vm_run;
 using namespace zpqdev;
 
 constexpr int WAVES = 4;                         // blocks per workgroup
+static_assert(ZPQ_MAX_COMP > 64, "CHUNKS keeps the coder in DCompScal[n], n <= 64: the record must exist in every slot");
 constexpr int L_STRETCH = 0;                     // u32[2048+128]
 constexpr int L_SQUASH = (2048 + 128) * 4;       // u16[4096]
 constexpr int L_NS = L_SQUASH + 4096 * 2;        // u8[1024]
@@ -163,6 +164,19 @@ __device__ __forceinline__ u32 sp_find(u32 *tags, const u32 cap, const u32 key, 
 // segment ends on a byte boundary (the decoder's EOF and overflow breaks included).
 // MIX / MIX2 / SSE entries never stay in registers beyond the bit that fetched them.  The format is the same for both
 // kernels: ZPQ_LANES_ROWS may change between two launches on one set.
+// CHUNKS (zpq_blockset_*_chunks on a ZPQ_SET_CHUNKS set, B.flags & ZB_CHUNK): KEEP also carries a member across a launch
+// boundary in the MIDDLE of a segment, as k_chain<..., KEEP> does (zpq_chain.hip).  A pause is at the top of a byte
+// iteration -- c8 == 1, hmap4 == 1, the context program run, MATCH's cxt 0, the rows written back -- so it adds to the above:
+//   DCompScal[i].pad_[1]   h[i], every lane's hctx (reset() zeroes h[] and leaves H alone: it cannot be reloaded from H)
+//   DCompScal[n]           the coder's low / high / code in a / b / c of the record BEHIND the last component's: a slot holds
+//                          ZPQ_MAX_COMP records whatever n is, n <= 64 here, and no kernel that runs on such a set touches a
+//                          record from n on (the last component itself may be a MATCH with every word of its own in use)
+// Both are stored by every launch under ZB_CHUNK and loaded by a member that goes on.  Per member, in the spare high bits of its
+// slot_map entry: ZB_MAP_CONT = its segment is open (no new coder, no priming reads, no reset(), no PP byte, whatever flags
+// says), ZB_MAP_MORE = encode: stop behind the last input byte, no compress(-1) / flush().  A decoder under ZB_CHUNK never
+// overflows: it leaves the byte loop behind the byte that filled its slab -- the overflow exit, one byte earlier --, in front
+// of the next EOF flag, and reports ZB_ST_PAUSED; with cap == 0 it runs no iteration but the one for a PP byte that opens a
+// segment.  Everything else sits in front of the byte loop and behind it.
 // (VMH stays the last template parameter: tests/test_kernel_resources.py finds the hash-chain instantiations by it.)
 //
 // (SP) Registers.  The dense forms fill their 128 registers; the probe needs some.  A lane is one component for good, so a
@@ -183,6 +197,9 @@ __device__ __forceinline__ u32 sp_find(u32 *tags, const u32 cap, const u32 key, 
 #define sse_i0 (SP ? st : own_sse_i0)
 #define sse_v0 (SP ? v0 : own_sse_v0)
 #define sse_v1 (SP ? v1 : own_sse_v1)
+// (CHUNKS) is there a PP byte in front of this launch's bytes: the flag, and in the KEEP forms not for a member that goes on;
+// the forms without KEEP read the flag where they always did and stay what they were instruction for instruction
+#define pp_on (KEEP ? (u32)pp : (B.flags & ZPQ_FLAG_PP))
 #define roff reinterpret_cast<u32 &>(mb)
 #define sp_claims reinterpret_cast<u32 &>(mlimit)
 template <bool DEC, bool KEEP, bool SP, bool VMH>
@@ -223,8 +240,12 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
     const int slot_id = blockIdx.x * WAVES + wave;
     const int nslots = B.nslots;
     // (KEEP: waves beyond the launch's blocks code nothing and do not read past the map)
-    const int slot_ix = KEEP ? (slot_id < B.nblocks ? B.slot_map[slot_id] : 0) : slot_id;
+    const int map_e = KEEP ? (slot_id < B.nblocks ? B.slot_map[slot_id] : 0) : 0;   // slot index | ZB_MAP_* (CHUNKS)
+    const int slot_ix = KEEP ? (map_e & ZB_MAP_SLOT) : slot_id;
     u8 *slot = B.slots + (u64)slot_ix * M.slot_bytes;
+    const bool chunk = KEEP && (B.flags & ZB_CHUNK) != 0;
+    const bool cont = chunk && (map_e & ZB_MAP_CONT) != 0;   // the member's segment is open: go on where it stopped
+    const bool more = chunk && (map_e & ZB_MAP_MORE) != 0;   // encode: the segment stays open behind this launch
 
     // this lane's component (predictor.v:239-265 as Predictor.init leaves it)
     const DComp &C = M.comp[act ? lane : 0];
@@ -301,10 +322,12 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
 
         u32 c8 = 1, hmap4 = 1, vm_prev = 0;
         u32 low = 1, high = 0xFFFFFFFFu, code = 0, opos = 0, ipos = 0, first = 0xFFFFFFFFu;
-        bool got_first = false;
-        if (DEC && lane == last)
+        bool got_first = KEEP && cont;                        // (CHUNKS: a member that goes on has no PP byte, the decoder's test below finds it taken)
+        const bool pp = KEEP && (B.flags & ZPQ_FLAG_PP) != 0 && !cont;   // (KEEP forms: pp_on)
+        if (DEC && lane == last && !(KEEP && cont))
             for (int k = 0; k < 4; k++) { u32 c = 0; if (ipos < nin) c = src[ipos++]; code = (code << 8) | c; }
-        const u32 total = DEC ? 0xFFFFFFFFu : nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u);
+        const u32 total = DEC ? ((KEEP && chunk && cap == 0u) ? (pp ? 1u : 0u) : 0xFFFFFFFFu) : nin + (pp_on ? 1u : 0u);
+        const u32 room = (KEEP && chunk) ? 1u : 0u;               // (CHUNKS: the decoder leaves with its slab full, not overflowing)
         DCompScal *gs = reinterpret_cast<DCompScal *>(slot + M.scal_off);
         DVmRegs *gr = reinterpret_cast<DVmRegs *>(slot + M.regs_off);
         if (KEEP) {                                               // what the last segment's launch left in the slot
@@ -314,6 +337,10 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
                     ma = gs[lane].a; mb = gs[lane].b; mc = gs[lane].c; mlimit = gs[lane].limit; mcxt = gs[lane].cxt;
                     mcur = ht[mlimit & (i32)(ht_len - 1)];
                 }
+            }
+            if (cont) {                                           // (CHUNKS) ... and what a pause left on top of it
+                if (act) hctx = gs[lane].pad_[1];
+                if (lane == last) { low = (u32)gs[n].a; high = (u32)gs[n].b; if (DEC) code = (u32)gs[n].c; }
             }
             if (VMH) vm_prev = gr->pad_[0];
             else { z.a = gr->a; z.b = gr->b; z.c = gr->c; z.d = gr->d; z.f = gr->f; z.pc = gr->pc; }
@@ -329,7 +356,7 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
         for (u32 bi = 0; bi < total; bi++) {
             u32 ch = 0;
             if (!DEC) {
-                if (B.flags & ZPQ_FLAG_PP) ch = (bi == 0) ? 0u : src[bi - 1];
+                if (pp_on) ch = (bi == 0) ? 0u : src[bi - 1];
                 else ch = src[bi];
             }
             // ---- EOF flag (encoder.v:108 / decoder.v:128)
@@ -665,11 +692,15 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
                 else {
                     if (lane == last && opos < cap) dst[opos] = (u8)byte;
                     opos++;
-                    if (opos > cap) break;
+                    if ((KEEP ? opos + room : opos) > cap) break;
                 }
             }
         }
-        if (!DEC && lane == last) {                               // compress(-1) + flush (encoder.v:101-105,130-139)
+        if (KEEP && chunk) {                                      // (CHUNKS) what a pause keeps on top of the KEEP state, as it stands here
+            if (act) gs[lane].pad_[1] = hctx;
+            if (lane == last) { gs[n].a = (i32)low; gs[n].b = (i32)high; gs[n].c = (i32)code; }
+        }
+        if (!DEC && lane == last && !(KEEP && more)) {            // compress(-1) + flush (encoder.v:101-105,130-139)
             high = low;
             while ((high ^ low) < 0x1000000u) {
                 if (opos < cap) dst[opos] = (u8)(high >> 24);
@@ -705,6 +736,8 @@ __global__ void __launch_bounds__(64 * WAVES, 4) k_lanes(const DBatch B, const L
             i32 stt = st0;
             if (SP && sp_refused && stt == ZPQ_OK) stt = ZPQ_E_TOOBIG;
             if (opos > cap && stt == ZPQ_OK) stt = ZPQ_E_OVERFLOW;
+            // (CHUNKS) the slab is full and the EOF not seen: the member stays open (the host: ZPQ_OK)
+            if (KEEP && DEC && chunk && opos >= cap && (!pp || got_first) && stt == ZPQ_OK) stt = ZB_ST_PAUSED;
             B.out_len[blk] = opos;
             B.status[blk] = stt;
             if (DEC) {
@@ -781,8 +814,12 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
     const int slot_id = (blockIdx.x * WAVES + wave) * RPW + row;
     const int nslots = B.nslots;
     // (KEEP: rows beyond the launch's blocks code nothing and do not read past the map)
-    const int slot_ix = KEEP ? (slot_id < B.nblocks ? B.slot_map[slot_id] : 0) : slot_id;
+    const int map_e = KEEP ? (slot_id < B.nblocks ? B.slot_map[slot_id] : 0) : 0;   // slot index | ZB_MAP_* (CHUNKS, see k_lanes)
+    const int slot_ix = KEEP ? (map_e & ZB_MAP_SLOT) : slot_id;
     u8 *slot = B.slots + (u64)slot_ix * M.slot_bytes;
+    const bool chunk = KEEP && (B.flags & ZB_CHUNK) != 0;    // wave-uniform; cont and more are the row's own
+    const bool cont = chunk && (map_e & ZB_MAP_CONT) != 0;
+    const bool more = chunk && (map_e & ZB_MAP_MORE) != 0;
 
     const DComp &C = M.comp[act ? li : 0];
     const int type = act ? C.type : 0;
@@ -852,10 +889,12 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
 
         u32 c8 = 1, hmap4 = 1, vm_prev = 0;
         u32 low = 1, high = 0xFFFFFFFFu, code = 0, opos = 0, ipos = 0, first = 0xFFFFFFFFu;
-        bool got_first = false;
-        if (DEC && li == last)
+        bool got_first = KEEP && cont;                        // (CHUNKS: a member that goes on has no PP byte, the decoder's test below finds it taken)
+        const bool pp = KEEP && (B.flags & ZPQ_FLAG_PP) != 0 && !cont;   // (KEEP forms: pp_on)
+        if (DEC && li == last && !(KEEP && cont))
             for (int k = 0; k < 4; k++) { u32 c = 0; if (ipos < nin) c = src[ipos++]; code = (code << 8) | c; }
-        const u32 total = DEC ? 0xFFFFFFFFu : nin + ((B.flags & ZPQ_FLAG_PP) ? 1u : 0u);
+        const u32 total = DEC ? ((KEEP && chunk && cap == 0u) ? (pp ? 1u : 0u) : 0xFFFFFFFFu) : nin + (pp_on ? 1u : 0u);
+        const u32 room = (KEEP && chunk) ? 1u : 0u;               // (CHUNKS: the decoder leaves with its slab full, not overflowing)
         DCompScal *gs = reinterpret_cast<DCompScal *>(slot + M.scal_off);
         DVmRegs *gr = reinterpret_cast<DVmRegs *>(slot + M.regs_off);
         if (KEEP) {                                               // what the last segment's launch left in the slot (see k_lanes)
@@ -866,6 +905,10 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
                     mcur = ht[mlimit & (i32)(ht_len - 1)];
                 }
             }
+            if (cont) {                                           // (CHUNKS) ... and what a pause left on top of it
+                if (act) hctx = gs[li].pad_[1];
+                if (li == last) { low = (u32)gs[n].a; high = (u32)gs[n].b; if (DEC) code = (u32)gs[n].c; }
+            }
             if (VMH) vm_prev = gr->pad_[0];
             else { z.a = gr->a; z.b = gr->b; z.c = gr->c; z.d = gr->d; z.f = gr->f; z.pc = gr->pc; }
         }
@@ -873,7 +916,7 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
         for (u32 bi = 0; bi < total; bi++) {
             u32 ch = 0;
             if (!DEC) {
-                if (B.flags & ZPQ_FLAG_PP) ch = (bi == 0) ? 0u : src[bi - 1];
+                if (pp_on) ch = (bi == 0) ? 0u : src[bi - 1];
                 else ch = src[bi];
             }
             i32 eof = 0;
@@ -1193,11 +1236,15 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
                 else {
                     if (li == last && opos < cap) dst[opos] = (u8)byte;
                     opos++;
-                    if (opos > cap) break;
+                    if ((KEEP ? opos + room : opos) > cap) break;
                 }
             }
         }
-        if (!DEC && li == last) {
+        if (KEEP && chunk) {                                      // (CHUNKS) what a pause keeps on top of the KEEP state (see k_lanes)
+            if (act) gs[li].pad_[1] = hctx;
+            if (li == last) { gs[n].a = (i32)low; gs[n].b = (i32)high; gs[n].c = (i32)code; }
+        }
+        if (!DEC && li == last && !(KEEP && more)) {
             high = low;
             while ((high ^ low) < 0x1000000u) {
                 if (opos < cap) dst[opos] = (u8)(high >> 24);
@@ -1223,6 +1270,7 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
             i32 stt = vm_st;
             if (SP && sp_refused && stt == ZPQ_OK) stt = ZPQ_E_TOOBIG;
             if (opos > cap && stt == ZPQ_OK) stt = ZPQ_E_OVERFLOW;
+            if (KEEP && DEC && chunk && opos >= cap && (!pp || got_first) && stt == ZPQ_OK) stt = ZB_ST_PAUSED;   // (CHUNKS, see k_lanes)
             B.out_len[blk] = opos;
             B.status[blk] = stt;
             if (DEC) {
@@ -1244,6 +1292,7 @@ __global__ void __launch_bounds__(64 * WAVES, VMH ? 4 : 2) k_rows(const DBatch B
 #undef sse_i0
 #undef sse_v0
 #undef sse_v1
+#undef pp_on
 #undef roff
 #undef sp_claims
 
