@@ -471,6 +471,12 @@ int zpq_tables_ex(int32_t *dt1024, int32_t *dt2k256, uint8_t *ns1024);
  * byte, the n context hashes Predictor.update copies out (predictor.v:809-816):
  * h_out[i*ncomp + k].  Exercises zpaql.v:167-954 alone. */
 int zpq_debug_contexts(zpq_ctx *, const zpq_model *, const uint8_t *in, size_t n, uint32_t *h_out);
+/* The pool's dirty-line logs (ZPQ_DIRTY_LOG_CAP, default 16384 entries per table, 0 = off): the dense level-2 kernels
+ * note which 64-byte table lines a launch made non-zero, and the next launch of theirs on the pool zeroes those lines
+ * instead of every slot.  This hook applies that clear to the pool's first nslots slots and counts the non-zero 16-byte
+ * words left in the part of them a launch expects zeroed: 0 when the logs name every dirty line.  ZPQ_E_ARG unless the
+ * last launches on the pool left valid logs for at least nslots slots. */
+int zpq_debug_pool_residue(zpq_ctx *, int nslots, uint64_t *count);
 /* Encode one fresh block with the generic kernel and record predict()'s return
  * value for the first ntrace modelled bits (predictor.v:536-668). */
 int zpq_debug_encode_trace(zpq_ctx *, const zpq_model *, const uint8_t *in, size_t n,

@@ -146,6 +146,8 @@ def lib():
     L.zpq_tables_ex.argtypes = [vp, vp, vp]
     L.zpq_debug_contexts.argtypes = [vp, vp, u8p, C.c_size_t, vp]
     L.zpq_debug_encode_trace.argtypes = [vp, vp, u8p, C.c_size_t, u32, vp, C.c_size_t, vp, vp, C.c_size_t]
+    if hasattr(L, "zpq_debug_pool_residue"):               # (a ZPQ_LIB_PATH build from before the dirty-line log lacks it)
+        L.zpq_debug_pool_residue.argtypes = [vp, i32, vp]
     L.zpq_status_string.argtypes = [i32]
     L.zpq_status_string.restype = C.c_char_p
     L.zpq_version.restype = C.c_char_p
@@ -449,6 +451,13 @@ class Context:
 
     def gather_dev(self, nblocks, d_src, d_src_off, d_len, d_dst, d_dst_off):
         _ck(lib().zpq_gather_dev(self.h, nblocks, d_src, d_src_off, d_len, d_dst, d_dst_off), "zpq_gather_dev")
+
+    def debug_pool_residue(self, nslots):
+        """Apply the dirty-line logs' clear to the pool's first `nslots` slots; the non-zero 16-byte words left (0 = the logs
+        name every dirty line).  ZpqError unless the last launches left valid logs for that many slots."""
+        count = C.c_uint64(0)
+        _ck(lib().zpq_debug_pool_residue(self.h, nslots, C.byref(count)), "zpq_debug_pool_residue")
+        return int(count.value)
 
     def debug_contexts(self, model, data):
         n = model.ncomp

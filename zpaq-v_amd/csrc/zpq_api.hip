@@ -28,6 +28,7 @@
 #include "../../include/zpaq_hip.h"
 #include "zpq_common.h"
 #include "zpq_host.h"
+#include "zpq_dev.h"
 
 #define ZPQ_SET_ALL (ZPQ_SET_LANES | ZPQ_SET_PIPE | ZPQ_SET_WAVES | ZPQ_SET_VMWAVES | ZPQ_SET_CHUNKS)
 
@@ -192,6 +193,16 @@ struct zpq_ctx {
     uint32_t sparse_cap = 0;               // line-store capacity (lines) for the largest block the caller submits
     uint32_t sparse_pct = 112;             // capacity = this percentage of the lines a largest block can touch (125: measured 4-7 % slower at levels 4-5, fewer blocks fit)
     DevBuf slots;
+    // The pool's dirty-line logs (DBatch::dlog, zpq_dev.h), beside the pool.  Slots [0, dlog_valid) hold what a launch of a
+    // log-keeping kernel left, for the device model dlog_model at dlog_cap entries per table, and their logs name every line
+    // of theirs that is not zero: the next such launch clears those lines alone.  Any other launch on the pool, a launch that
+    // failed, a pool or log buffer that was reallocated or released, and a new state budget make it 0 (dlog_drop).
+    DevBuf dlog;
+    const DModel *dlog_model = nullptr;    // (the device copy: one per model and layout)
+    DModel dlog_layout;                    // ... and the layout it holds (zpq_debug_pool_residue)
+    uint32_t dlog_cap = 0;
+    int dlog_valid = 0;
+    void dlog_drop() { dlog_valid = 0; dlog_model = nullptr; }
     uint64_t budget = 0;
     int last_slots = 0;
     unsigned last_host = 0;                // what host_pipeline did with the last host-pointer batch (zpq_ctx_last_host_transfer)
@@ -388,6 +399,7 @@ extern "C" int zpq_ctx_set_state_budget(zpq_ctx *c, uint64_t bytes) try
 {
     if (!ctx_live(c)) return ZPQ_E_ARG;
     c->budget = bytes;
+    c->dlog_drop();
     return ZPQ_OK;
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 extern "C" int zpq_ctx_set_max_block_bytes(zpq_ctx *c, uint64_t bytes) try
@@ -457,6 +469,14 @@ static bool request(const char *var, uint32_t flags, uint32_t bit)
     const char *ev = getenv(var);
     const bool env = ev && (ev[0] == '0' || ev[0] == '1');
     return env ? ev[0] == '1' : (flags & bit) != 0;
+}
+// ZPQ_DIRTY_LOG_CAP: entries per table of the dirty-line log (default 16384; 0 = no log, the kernels as they were)
+static uint32_t dirty_log_cap()
+{
+    const char *ev = getenv("ZPQ_DIRTY_LOG_CAP");
+    if (!ev || !*ev) return 16384u;
+    const long v = atol(ev);
+    return v <= 0 ? 0u : (v > (1l << 20) ? (1u << 20) : (uint32_t)v);
 }
 struct SparseKnobs {
     uint32_t forced_cap = 0;               // ZPQ_SPARSE_FORCE_LOG2 = 8 .. 25 (tests: exercise the store on small models), else 0
@@ -696,19 +716,72 @@ static int run_batch(zpq_ctx *c, const zpq_model *m, int decode, const BatchArgs
     B.prog_counter = (P.fam == F_CHAIN && decode) ? a.prog_counter : nullptr;   // (other kernels do not report: the host then copies after the kernel)
     B.prog_pos = a.prog_pos;
 
+    B.nslots = P.nslots;
     if (a.x.own_slot) {
         B.slots = a.x.own_slot;
     } else {
+        const size_t had = c->slots.cap;
         rc = c->slots.ensure((size_t)P.nslots * P.M.slot_bytes + 256);   // (the slack a MIX row read needs is part of slot_bytes: zpq_model.cpp mix_row_pad)
+        if (c->slots.cap != had) c->dlog_drop();                 // (a new pool: nobody knows what is in it)
         if (rc != ZPQ_OK) return rc;
         B.slots = (uint8_t *)c->slots.p;
     }
-    B.nslots = P.nslots;
+    // The dirty-line log: offered to a launch that keeps it (the dense level-2 pair), whose slots then enter with a valid log
+    // where the last launches on the pool kept it too, for this model, at this capacity.  Without room for the log the launch
+    // runs as it always did.
+    bool logged = false;
+    if (!a.x.own_slot) {
+        const uint32_t cap = dirty_log_cap();
+        if (cap && P.fam == F_CHAIN && !P.sp && zpq_chain_keeps_dlog(&B, &P.M, decode, P.bpw)) {
+            const size_t had = c->dlog.cap;
+            const int lrc = c->dlog.ensure((size_t)P.nslots * 3 * zpqdev::dlog_stride(cap) * 4);
+            if (c->dlog.cap != had || cap != c->dlog_cap || dm.d_model != c->dlog_model) c->dlog_drop();
+            if (lrc == ZPQ_OK) {
+                logged = true;
+                B.dlog = (uint32_t *)c->dlog.p; B.dlog_cap = cap; B.dlog_valid = c->dlog_valid;
+            }
+        }
+    }
     c->last_slots = P.nslots;
     c->last_sp = P.sp;
     c->last_host = 0;                                            // (host_pipeline sets it when its batch is through)
-    return launch_family(c, B, P, decode, c->stream);
+    rc = launch_family(c, B, P, decode, c->stream);
+    if (!a.x.own_slot) {
+        if (rc != ZPQ_OK || !logged) c->dlog_drop();             // (a launch on fewer slots than are valid keeps the others valid)
+        else {
+            if (c->dlog_model != dm.d_model) c->dlog_layout = P.M;
+            c->dlog_model = dm.d_model; c->dlog_cap = B.dlog_cap;
+            c->dlog_valid = std::max(c->dlog_valid, P.nslots);
+        }
+    }
+    return rc;
 }
+
+// debug (tests): apply the log-clear to the pool's first nslots slots and count the non-zero 16-byte words left in their
+// zero_bytes -- 0 if the logs name every dirty line.  ZPQ_E_ARG unless that many slots hold valid logs.
+extern "C" int zpq_debug_pool_residue(zpq_ctx *c, int nslots, uint64_t *count) try
+{
+    if (!ctx_live(c) || !count || nslots < 1) return ZPQ_E_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (nslots > c->dlog_valid || !c->dlog_model || !c->dlog.p || !c->slots.p) return ZPQ_E_ARG;
+    HIPCK(hipSetDevice(c->device));
+    unsigned long long *d_count = nullptr;
+    HIPCK(hipMalloc((void **)&d_count, 8));
+    DBatch B;
+    memset(&B, 0, sizeof B);
+    B.model = c->dlog_model; B.slots = (uint8_t *)c->slots.p; B.nslots = nslots;
+    B.dlog = (uint32_t *)c->dlog.p; B.dlog_cap = c->dlog_cap; B.dlog_valid = c->dlog_valid;
+    int rc = ZPQ_OK;
+    unsigned long long h = 0;
+    if (hipMemsetAsync(d_count, 0, 8, c->stream) != hipSuccess) rc = ZPQ_E_NODEVICE;
+    if (rc == ZPQ_OK) rc = zpq_launch_dlog_residue(&B, &c->dlog_layout, nslots, d_count, c->stream);
+    if (rc == ZPQ_OK && (hipGetLastError() != hipSuccess || hipMemcpyAsync(&h, d_count, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                         hipStreamSynchronize(c->stream) != hipSuccess)) rc = ZPQ_E_NODEVICE;
+    (void)hipFree(d_count);
+    if (rc != ZPQ_OK) { c->dlog_drop(); return rc; }
+    *count = h;
+    return ZPQ_OK;
+} ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
 extern "C" int zpq_encode_blocks_dev(zpq_ctx *c, const zpq_model *m, int nblocks, const uint8_t *in,
                                      const uint64_t *in_off, uint32_t flags, uint8_t *out,
@@ -1409,6 +1482,8 @@ extern "C" int zpq_blockset_create_ex(zpq_ctx *c, const zpq_model *m, int nmembe
         (void)hipGetLastError();
         (void)hipStreamSynchronize(c->stream);
         c->slots.release();                                 // the idle slot pool makes room; it grows back on demand
+        c->dlog.release();
+        c->dlog_drop();
         if (hipMalloc((void **)&s->slots, s->bytes) != hipSuccess) { (void)hipGetLastError(); delete s; return ZPQ_E_NOMEM; }
     }
     int rc = ZPQ_OK;

@@ -124,10 +124,29 @@ struct BitCtx {
 // and which stay open (ZB_MAP_MORE: no compress(-1) / flush()) is per member, in the spare high bits of the slot_map entries;
 // under ZB_CHUNK a decoder whose slab is full leaves the byte loop behind the byte that filled it, in front of the next EOF
 // flag (the overflow exit, one byte earlier), and reports ZB_ST_PAUSED.
-template <bool DEC, bool SPEC, int NCH, bool MIXT, int GG, bool SP, bool HIO = false, bool KEEP = false>
-__global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg cfg)
+// DLOG = the launch keeps the slots' dirty-line logs (zpq_dev.h; the dense two-hypothesis decoder of the chain of three, level 2).
+// A row that find_ht hands out with no state in it -- a fresh line's, or a victim's started over -- has its line's offset
+// appended when the row is written back, by what was noted when the row was chosen; the count stops at the capacity, which
+// says "overflowed".  A written row holds non-zero states ever after, so a line is logged
+// at its first touch (and again when a row of it is replaced: duplicates are harmless).  Copy 0 of a component stores and
+// its count is the one written, once, behind the byte loop.  The clear in front of a block zeroes the slot's logged lines
+// instead of the whole slot where the slot's log is valid: from the group's second block on, and for its first block if
+// the host vouches for the slot.
+// The DLOG form is built in a translation unit of its own (zpq_chain_log.hip, which includes this file) and is called k_lchain
+// there: one template text, and the kernels without the flag keep their names, their number and their code.
+#ifdef ZPQ_CHAIN_LOG_TU
+#define ZPQ_K_CHAIN k_lchain
+#else
+#define ZPQ_K_CHAIN k_chain
+#endif
+template <bool DEC, bool SPEC, int NCH, bool MIXT, int GG, bool SP, bool HIO = false, bool KEEP = false, bool DLOG = false>
+__global__ void __launch_bounds__(64 * MAXW) ZPQ_K_CHAIN(const DBatch B, const Cfg cfg)
 {
+#ifndef ZPQ_CHAIN_LOG_TU
+    static_assert(!DLOG, "the log-keeping form is k_lchain (zpq_chain_log.hip)");
+#endif
     static_assert(!(KEEP && HIO), "block sets take no part in striped transfers");
+    static_assert(!DLOG || (DEC && !SPEC && NCH == 3 && !MIXT && GG == 8 && !SP && !HIO && !KEEP), "the log is kept by level 2's dense decoder");
     constexpr int G = GG;            // shadows zpqc::G inside the kernel
     constexpr int BPW = 64 / GG;
     extern __shared__ __align__(16) u8 lds[];
@@ -298,6 +317,12 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
             uint4 *z4 = reinterpret_cast<uint4 *>(slot);
             const u64 n16 = M.zero_bytes / 16;
             const uint4 zero = make_uint4(0, 0, 0, 0);
+            if (DLOG && (blk != slot_id || slot_id < B.dlog_valid)) {
+                if constexpr (DLOG) {
+                    dlog_zero_rest(M, slot, NCH, (u32)li, G);
+                    for (int c = 0; c < NCH; c++) dlog_clear_table(B, M, slot, slot_id, c, NCH, (u32)li, G);
+                }
+            } else
             for (u64 i = li; i < n16; i += G) z4[i] = zero;
             for (int c = 0; c < n; c++) {
                 const DComp &cc = M.comp[c];
@@ -578,6 +603,13 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
         const bool wr_lane = hashed && (!HYP || hyp == 0);  // this lane writes finished rows back
         const bool mix_lane = ctype == ZT_MIX2;
         bool row_mine = true;                              // this copy requested the rows of the nibble that really follows
+        u32 *dl_tab = nullptr;                             // DLOG: this lane's table's log, its count, "the row in hand came without states"
+        u32 dl_cnt = 0, dl_cap = 0;
+        bool dl_fresh = false;
+        if constexpr (DLOG) {
+            dl_tab = dlog_table(B, slot_id, lc < NCH ? lc : 0, NCH);   // (a lane without a table stores nothing)
+            dl_cap = B.dlog_cap;
+        }
         // (Asking for a byte's second-nibble rows two bit steps early -- four neighbouring lines per table instead of two: buys
         //  nothing on the dieted kernel and reads a third more lines -- EXPERIMENTS.md 4.1 `HYP4` and R4.11.)
         auto take_prefetched = [&](const bool have_prev) {
@@ -646,6 +678,13 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
 #ifndef ZPQ_DEBUG_NO_ROWS
             // (one predicate, the lane's part of it computed once: `have_prev && hashed && ...` as written became a twenty-instruction
             //  maze of exec-mask moves around one store)
+            if constexpr (DLOG) {
+                // (the entry under its own predicate: stored with every row at the count's place it cost 7.7 ms of the 231 ms
+                //  decode, like this 4.0 -- EXPERIMENTS.md R23)
+                if (have_prev & wr_lane) *reinterpret_cast<u32x4 *>(tbase + poff2) = Rp;
+                if ((have_prev & wr_lane) && dl_fresh && dl_cnt < dl_cap) { dl_tab[DLOG_HDR + dl_cnt] = poff2 & ~63u; dl_cnt++; }
+                dl_fresh = ((X.r0 >> 8) | X.r1 | X.r2 | X.r3) == 0u;
+            } else
             if (have_prev & wr_lane) *reinterpret_cast<u32x4 *>(tbase + poff2) = Rp;   // (both copies hold the same row: copy 0 writes)
 #endif
         };
@@ -1427,6 +1466,9 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
 
         if (DEC && pend_store) dst[pend_pos] = (u8)pend_val;
         // (the last nibble's row is not written back: the slot is re-initialised for the next block)
+        if constexpr (DLOG) {
+            if (wr_lane) dl_tab[0] = dl_cnt;                  // the block's count, once
+        }
         if constexpr (KEEP) {
             // ---- ... unless the block goes on in a later launch: everything that lives in registers and LDS into the slot.
             // Two hypotheses: both copies hold the same row, hash and bookkeeping after the take-over; copy 0 saves.
@@ -1511,6 +1553,15 @@ __global__ void __launch_bounds__(64 * MAXW) k_chain(const DBatch B, const Cfg c
 #undef ZPQ_IS_PP
 }  // namespace zpqc
 
+#ifdef ZPQ_CHAIN_LOG_TU
+// ------------------------------------------------------------------ zpq_chain_log.hip: the one kernel of this unit and its launch
+extern "C" int zpq_launch_lchain(const DBatch *B, const zpqc::Cfg *cfg, int nwg, int threads, size_t lds, hipStream_t stream)
+{
+    (void)hipFuncSetAttribute((const void *)zpqc::k_lchain<true, CHAIN_SPEC_DEC, 3, false, 8, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL((zpqc::k_lchain<true, CHAIN_SPEC_DEC, 3, false, 8, false, false, false, true>), dim3(nwg), dim3(threads), lds, stream, *B, *cfg);
+    return ZPQ_OK;
+}
+#else
 // ------------------------------------------------------------------ host side
 using zpqc::Cfg;
 
@@ -1655,6 +1706,59 @@ extern "C" int zpq_chain_has_hio(const DModel *M)
     return build_cfg(M, &cfg) && !cfg.sparse && (cfg.nch_spec == 2 || cfg.nch_spec == 3) ? 1 : 0;
 }
 
+// Would zpq_launch_chain run this batch on a kernel that keeps the dirty-line log (DBatch::dlog)?  The dense chain of three
+// (level 2) without striped transfers and outside block sets: its encoder on k_pipe (zpq_pipe_keeps_dlog), its decoder on the
+// two-hypothesis k_chain.  Every other kernel of the family -- k_chain<encode> below twelve blocks, k_pipe2, k_dpipe, the
+// line store, the other chain lengths, the runtime-loop chain, the KEEP and HIO forms -- keeps none.
+extern "C" int zpq_chain_keeps_dlog(const DBatch *B, const DModel *hostM, int decode, int blocks_per_wg)
+{
+#ifdef ZPQ_NO_HYP
+    if (decode) return 0;
+#endif
+    Cfg cfg;
+    if (!build_cfg(hostM, &cfg) || cfg.sparse || cfg.has_mix2 || cfg.nch_spec != 3 || cfg.g != 8) return 0;
+    if ((B->flags & ZB_KEEP_STATE) || B->gate_flag || B->prog_counter) return 0;
+    if (!decode) return zpq_pipe_keeps_dlog(B, hostM, blocks_per_wg);
+    return zpq_dpipe_applies(hostM, blocks_per_wg, B->nslots) ? 0 : 1;
+}
+
+namespace zpqc {
+// debug (zpq_debug_pool_residue): a workgroup per slot applies the log-clear and resets the counts ...
+template <int NT>
+__global__ void __launch_bounds__(256) k_dlog_apply(const DBatch B)
+{
+    const DModel &M = *B.model;
+    const int s = blockIdx.x;
+    u8 *slot = B.slots + (u64)s * M.slot_bytes;
+    dlog_zero_rest(M, slot, NT, threadIdx.x, blockDim.x);
+    for (int c = 0; c < NT; c++) dlog_clear_table(B, M, slot, s, c, NT, threadIdx.x, blockDim.x);
+    __syncthreads();
+    if (threadIdx.x < NT) dlog_table(B, s, (int)threadIdx.x, NT)[0] = 0u;
+}
+// ... and the non-zero 16-byte words left in the slots' zero_bytes are counted
+__global__ void __launch_bounds__(256) k_dlog_residue(const DBatch B, unsigned long long *count)
+{
+    const DModel &M = *B.model;
+    const uint4 *z4 = reinterpret_cast<const uint4 *>(B.slots + (u64)blockIdx.y * M.slot_bytes);
+    const u64 n16 = M.zero_bytes / 16;
+    u32 nz = 0;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (u64)gridDim.x * blockDim.x) {
+        const uint4 v = z4[i];
+        nz += (v.x | v.y | v.z | v.w) != 0u ? 1u : 0u;
+    }
+    if (nz) atomicAdd(count, (unsigned long long)nz);
+}
+}  // namespace zpqc
+
+extern "C" int zpq_launch_dlog_residue(const DBatch *B, const DModel *hostM, int nslots, unsigned long long *d_count, hipStream_t stream)
+{
+    Cfg cfg;
+    if (!build_cfg(hostM, &cfg) || cfg.sparse || cfg.has_mix2 || cfg.nch_spec != 3 || !B->dlog || nslots < 1) return ZPQ_E_INTERNAL;
+    hipLaunchKernelGGL((zpqc::k_dlog_apply<3>), dim3(nslots), dim3(256), 0, stream, *B);
+    hipLaunchKernelGGL(zpqc::k_dlog_residue, dim3(64, nslots), dim3(256), 0, stream, *B, d_count);
+    return ZPQ_OK;
+}
+
 // (zpq_pipe.hip: the wave-pipelined encoder of the chains without a MIX2; zpq_dpipe.hip: the wave-split decoder of the
 // dense chains without a MIX2 -- both declared in zpq_host.h)
 extern "C" int zpq_launch_chain(const DBatch *B, const DModel *hostM, int decode, int nwg, int blocks_per_wg,
@@ -1679,6 +1783,7 @@ extern "C" int zpq_launch_chain(const DBatch *B, const DModel *hostM, int decode
     // the pipeline's floor of members, k_pipe<..., KEEP>: the two keep the same state format, so the choice is per call
     const bool keep = (B->flags & ZB_KEEP_STATE) != 0;
     if (keep && (hio || B->nslots < B->nblocks)) return ZPQ_E_INTERNAL;   // one block per slot and launch
+    if (B->dlog && !zpq_chain_keeps_dlog(B, hostM, decode, blocks_per_wg)) return ZPQ_E_INTERNAL;   // (the host offers the log to a kernel that keeps it)
     if (keep && !decode && (B->flags & ZB_SET_PIPE) && B->slot_map && zpq_pipe_applies(hostM, blocks_per_wg, B->nslots)) {
         return zpq_launch_pipe(B, hostM, nwg, blocks_per_wg, stream, name_out);   // "k_pipe<encode>"
     }
@@ -1736,6 +1841,9 @@ extern "C" int zpq_launch_chain(const DBatch *B, const DModel *hostM, int decode
             break;                                                                                       \
         }                                                                                                \
     } while (0)
+    if (B->dlog) {                                          // (decode, the dense chain of three: zpq_chain_keeps_dlog)
+        return zpq_launch_lchain(B, &cfg, nwg, threads, lds, stream);   // k_lchain (zpq_chain_log.hip)
+    }
     if (decode) ZPQ_DISPATCH(true); else ZPQ_DISPATCH(false);
 #undef ZPQ_DISPATCH
 #undef ZPQ_LAUNCH_SP
@@ -1744,3 +1852,4 @@ extern "C" int zpq_launch_chain(const DBatch *B, const DModel *hostM, int decode
 #undef ZPQ_LAUNCH_K
     return ZPQ_OK;
 }
+#endif   // ZPQ_CHAIN_LOG_TU

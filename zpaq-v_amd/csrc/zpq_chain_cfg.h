@@ -2,6 +2,7 @@
 // component) share: the LDS layout of the read-only tables and of a block's counters / weights, and the launch
 // configuration the host derives from a model (zpq_chain_build_cfg in zpq_chain.hip).
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "zpq_common.h"
@@ -50,3 +51,11 @@ struct Cfg {
 
 // false = the model is not a chain the kernels handle (-> lanes / generic kernel)
 bool zpq_chain_build_cfg(const DModel *M, zpqc::Cfg *cfg);
+
+// The kernels that keep the dirty-line log (DBatch::dlog) are built in units of their own under names of their own --
+// zpq_chain_log.hip: k_lchain, zpq_pipe_log.hip: k_lpipe (layout = the launch's zpqp::PipeLds) -- and launched from
+// zpq_launch_chain / zpq_launch_pipe through these.
+extern "C" {
+int zpq_launch_lchain(const DBatch *B, const zpqc::Cfg *cfg, int nwg, int threads, size_t lds, hipStream_t stream);
+int zpq_launch_lpipe(const DBatch *B, const zpqc::Cfg *cfg, const void *layout, int nwg, size_t lds, hipStream_t stream);
+}

@@ -99,6 +99,12 @@ struct DBatch {
     // memory); when the count reaches the number of blocks the host copies that stripe out beside the running kernel.
     uint32_t prog_pos;
     uint32_t *prog_counter;      // null = no progress reports
+    // Dirty-line log (the dense level-2 pair k_pipe<encode> / two-hypothesis k_chain<decode> only; zpq_dev.h): per slot and
+    // hashed table a count and up to dlog_cap offsets of the 64-byte lines a launch made non-zero, so that the next launch
+    // on the pool zeroes those lines instead of the whole slot.  Slots [0, dlog_valid) enter the launch with valid logs.
+    uint32_t *dlog;              // null = no log: the kernels as they were
+    uint32_t dlog_cap;
+    int32_t dlog_valid;
 };
 
 #define ZB_KEEP_STATE 0x100u     // do not re-initialise the slot (later segments of one block)

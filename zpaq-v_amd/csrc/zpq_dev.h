@@ -59,4 +59,66 @@ __device__ __forceinline__ void slot_match_init(const DModel &M, uint8_t *slot, 
         if (M.comp[ci].type == ZT_MATCH) { gs[ci].a = M.comp[ci].a; gs[ci].b = M.comp[ci].b; }
 }
 
+
+// ---- The dirty-line log (DBatch::dlog).  Invariant: after a launch that keeps the log, every byte of a slot's zero_bytes
+// is zero except in the 64-byte lines of hashed table c whose offsets are entries [0, count) of the slot's log for c;
+// count == dlog_cap says the log overflowed and the whole table may be dirty.  Per slot and table: DLOG_HDR words (word 0 =
+// count), then the entries (room rounded up to four: a thread reads four entries with one load).  The tables are the
+// model's components [0, nt), all hashed (a chain without a MIX2).
+constexpr uint32_t DLOG_HDR = 16;
+__host__ __device__ __forceinline__ uint64_t dlog_stride(const uint32_t cap) { return DLOG_HDR + (((uint64_t)cap + 3u) & ~3ull); }
+__device__ __forceinline__ uint32_t *dlog_table(const DBatch &B, const int slot_id, const int c, const int nt)
+{
+    return B.dlog + ((uint64_t)slot_id * (uint32_t)nt + (uint32_t)c) * dlog_stride(B.dlog_cap);
+}
+// zero the logged lines of one table: a thread takes four entries per load and whole lines, two loads in flight (the
+// entry is a dependent load in front of its stores: one at a time the loop would run at one memory round trip per line)
+__device__ __forceinline__ void dlog_zero_lines(uint8_t *tb, const uint32_t ht_len, const uint32_t *lg, const uint32_t cnt,
+                                                const uint32_t first, const uint32_t stride)
+{
+    const uint4 zero = make_uint4(0, 0, 0, 0);
+    const uint32_t mask = ht_len - 64u;                    // (a table is a power of two of at least one line: no entry leaves it)
+    const uint4 *e4 = reinterpret_cast<const uint4 *>(lg + DLOG_HDR);
+    const uint32_t nq = (cnt + 3u) >> 2;
+    auto z = [&](const uint32_t idx, const uint32_t off) {
+        if (idx < cnt) {
+            uint4 *l = reinterpret_cast<uint4 *>(tb + (off & mask));
+            l[0] = zero; l[1] = zero; l[2] = zero; l[3] = zero;
+        }
+    };
+    for (uint32_t q = first; q < nq; q += 2u * stride) {
+        const uint32_t q1 = q + stride;
+        const uint4 a = e4[q];
+        const uint4 b = e4[min(q1, nq - 1u)];
+        z(4u * q, a.x); z(4u * q + 1u, a.y); z(4u * q + 2u, a.z); z(4u * q + 3u, a.w);
+        if (q1 < nq) { z(4u * q1, b.x); z(4u * q1 + 1u, b.y); z(4u * q1 + 2u, b.z); z(4u * q1 + 3u, b.w); }
+    }
+}
+__device__ __forceinline__ void dlog_zero_range(uint8_t *slot, const uint64_t from, const uint64_t to, const uint32_t first, const uint32_t stride)
+{
+    uint4 *z4 = reinterpret_cast<uint4 *>(slot + from);
+    const uint64_t n16 = to > from ? (to - from) / 16 : 0;
+    const uint4 zero = make_uint4(0, 0, 0, 0);
+    for (uint64_t i = first; i < n16; i += stride) z4[i] = zero;
+}
+// what of a slot no table holds: in front of, between and behind the tables (components lie in the slot in their order)
+__device__ __forceinline__ void dlog_zero_rest(const DModel &M, uint8_t *slot, const int nt, const uint32_t first, const uint32_t stride)
+{
+    uint64_t from = 0;
+    for (int c = 0; c < nt; c++) {
+        dlog_zero_range(slot, from, M.comp[c].ht_off, first, stride);
+        from = M.comp[c].ht_off + M.comp[c].ht_len;
+    }
+    dlog_zero_range(slot, from, M.zero_bytes, first, stride);
+}
+// one table of a slot whose log is valid: its logged lines, or all of it after an overflow
+__device__ __forceinline__ void dlog_clear_table(const DBatch &B, const DModel &M, uint8_t *slot, const int slot_id, const int c, const int nt,
+                                                 const uint32_t first, const uint32_t stride)
+{
+    const uint32_t *lg = dlog_table(B, slot_id, c, nt);
+    const uint32_t cnt = lg[0];
+    if (cnt >= B.dlog_cap) dlog_zero_range(slot, M.comp[c].ht_off, M.comp[c].ht_off + M.comp[c].ht_len, first, stride);
+    else dlog_zero_lines(slot + M.comp[c].ht_off, M.comp[c].ht_len, lg, cnt, first, stride);
+}
+
 }  // namespace zpqdev

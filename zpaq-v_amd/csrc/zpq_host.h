@@ -61,6 +61,12 @@ int zpq_chain_has_hio(const DModel *M);   // kernels that take part in striped h
 int zpq_pipe_shape_applies(const DModel *M);   // the chain is one of the shapes k_pipe codes
 int zpq_pipe_applies(const DModel *M, int blocks_per_wg, int nslots);
 int zpq_launch_pipe(const DBatch *B, const DModel *hostM, int nwg, int blocks_per_wg, hipStream_t stream, const char **name_out);
+// the dirty-line log (DBatch::dlog): would the launch keep it?  (B->dlog itself is not looked at: the host asks before it offers one)
+int zpq_pipe_keeps_dlog(const DBatch *B, const DModel *hostM, int blocks_per_wg);
+int zpq_chain_keeps_dlog(const DBatch *B, const DModel *hostM, int decode, int blocks_per_wg);
+// debug: log-clear slots [0, nslots) of a pool whose logs are valid for d_model (a chain of nt hashed tables), reset their
+// counts, and count the non-zero 16-byte words left in their zero_bytes into *d_count
+int zpq_launch_dlog_residue(const DBatch *B, const DModel *hostM, int nslots, unsigned long long *d_count, hipStream_t stream);
 int zpq_dpipe_applies(const DModel *M, int blocks_per_wg, int nslots);
 int zpq_launch_dpipe(const DBatch *B, const DModel *hostM, int nwg, int blocks_per_wg, hipStream_t stream);
 // zpq_lanes.hip: lane i = component i (k_rows: four blocks per wave, k_lanes), and the KEEP forms for block sets

@@ -155,9 +155,13 @@ struct Req {
 // IS_LAST: the component the coder follows (its link carries squash(p) and the bit).  FWD_PIN: the last ISSE of a chain
 // that a MIX2 follows: it hands its INPUT on as well (the MIX2 mixes p[n-3] and p[n-2], levels.v:199-218,290-375).
 // KEEP: the block goes on from the state an earlier launch left in its slot and leaves its own there (k_pipe).
-template <int NCH, bool SP, bool HIO, bool IS_ICM, bool IS_LAST, bool FWD_PIN, bool KEEP = false>
+// DLOG: the stage keeps its table's dirty-line log (zpq_dev.h): a row that find_ht hands out all zero -- a fresh line's, or
+// a victim's that was never written -- has its line's offset appended (a written row holds non-zero states ever after, so a
+// line is logged at its first touch; duplicates are harmless).  The count stops at the capacity, which says "overflowed".
+template <int NCH, bool SP, bool HIO, bool IS_ICM, bool IS_LAST, bool FWD_PIN, bool KEEP = false, bool DLOG = false>
 __device__ __forceinline__ void comp_loop(const StageArgs &S)
 {
+    static_assert(!DLOG || (!SP && !KEEP && !HIO), "the log is kept by the dense one-launch stages");
     const DBatch &B = *S.B;
     const Cfg &cfg = *S.cfg;
     const DModel &M = *B.model;
@@ -206,6 +210,12 @@ __device__ __forceinline__ void comp_loop(const StageArgs &S)
     bool sp_full = false;
     u32 sp_claims = 0;
     const u32 sp_limit = ZPQ_SP_LIMIT(sp_cap);
+    u32 *dl_tab = nullptr;
+    u32 dl_cnt = 0, dl_cap = 0;
+    if constexpr (DLOG) {
+        dl_tab = dlog_table(B, (int)blockIdx.x * S.bpw + S.lane, ci, NCH);   // (a lane without a slot never uses it)
+        dl_cap = B.dlog_cap;
+    }
     if constexpr (KEEP) {
         // the hash program's registers, and the store's claim count and full flag, where k_chain<..., KEEP> keeps them
         // (Every stage reads the same two words, and the ICM's wave writes them behind its byte loop: a stage has used its
@@ -264,6 +274,12 @@ __device__ __forceinline__ void comp_loop(const StageArgs &S)
         asm volatile("; order: row store after the prefetched rows are consumed" : "+v"(poff2), "+v"(cpo) : "v"(R.x), "v"(R.w));
         if (SP && claim) ZPQ_SP_CLAIM(sp_tags, claim_si, q.key, tbase + cpo);
         if (!NO_ROWS && have1) *reinterpret_cast<u32x4 *>(tbase + poff2) = u32x4{L1.x, L1.y, L1.z, L1.w};
+        if constexpr (DLOG) {
+            // (A store under the predicate, behind the row store and with no load in its region.  The branch-free form -- the
+            //  entry stored every nibble at the count's place -- was measured first: 64 lanes are 64 logs, so it is one more
+            //  scattered request per lane and nibble, +13 ms on the 119 ms encode; this one costs 3.6 ms.  EXPERIMENTS.md R23.)
+            if (Rx == 0u && dl_cnt < dl_cap) { dl_tab[DLOG_HDR + dl_cnt] = cpo; dl_cnt++; }
+        }
         return R;
     };
     // the shipped program shape's context for this component (zpq_rows.h: the hash chain, level 1's program)
@@ -434,6 +450,9 @@ __device__ __forceinline__ void comp_loop(const StageArgs &S)
     if (HIO && phase == 0 && B.gate_flag && !gate_wait(B.gate_flag)) status = ZPQ_E_INTERNAL;
     }   // phase
     // (the last nibbles' rows are not written back: the slot is re-initialised for the next block)
+    if constexpr (DLOG) {
+        if (S.active) dl_tab[0] = dl_cnt;                  // the block's count, once
+    }
     if constexpr (KEEP) {
         // ... unless the block goes on in a later launch.  The byte's first nibble was stored when its second was consumed
         // (consume stores its L1, have1 = true there), so only the second one is still in registers -- under FWD2 too: the
@@ -869,10 +888,24 @@ __device__ __forceinline__ void coder_loop(const StageArgs &S, Coder &X) { coder
 // the LDS packing, prev / m4, b4 and the stores' claim counts into the stages; hash tables, tags, lines and the MIX2's weights
 // are used where they are.  Save: all of that back, with the rows and weights still in registers.  c8, hmap4, the context
 // hashes and the coder start again with every segment (predictor.v:827-833, compressor.v:238-245).  The byte loop is the same code.
-template <int NCH, bool MIXT, bool SP, bool HIO, bool KEEP = false>
-__global__ void __launch_bounds__(64 * (NCH + (MIXT ? 2 : 1))) k_pipe(const DBatch B, const Cfg cfg, const PipeLds L)
+// DLOG = the launch keeps the slots' dirty-line logs (zpq_dev.h; the dense chain of three, level 2): the component stages log
+// (comp_loop), and the clear in front of a round zeroes a slot's logged lines instead of the whole slot where the slot's log
+// is valid -- it is from the launch's second round on, and in the first for the slots the host vouches for.
+// The DLOG form is built in a translation unit of its own (zpq_pipe_log.hip, which includes this file) and is called k_lpipe
+// there: one template text, and the kernels without the flag keep their names, their number and their code.
+#ifdef ZPQ_PIPE_LOG_TU
+#define ZPP_K_PIPE k_lpipe
+#else
+#define ZPP_K_PIPE k_pipe
+#endif
+template <int NCH, bool MIXT, bool SP, bool HIO, bool KEEP = false, bool DLOG = false>
+__global__ void __launch_bounds__(64 * (NCH + (MIXT ? 2 : 1))) ZPP_K_PIPE(const DBatch B, const Cfg cfg, const PipeLds L)
 {
+#ifndef ZPQ_PIPE_LOG_TU
+    static_assert(!DLOG, "the log-keeping form is k_lpipe (zpq_pipe_log.hip)");
+#endif
     static_assert(!(KEEP && HIO), "block sets take no part in striped transfers");
+    static_assert(!DLOG || (!MIXT && !SP && !HIO && !KEEP), "the log is kept by the dense one-launch chains");
     extern __shared__ __align__(16) u8 lds[];
     const DModel &M = *B.model;
     const int tid = threadIdx.x, nthr = blockDim.x;
@@ -933,7 +966,29 @@ __global__ void __launch_bounds__(64 * (NCH + (MIXT ? 2 : 1))) k_pipe(const DBat
         } else {
             const u64 n16 = M.zero_bytes / 16;
             const uint4 zero = make_uint4(0, 0, 0, 0);
-            for (int b = 0; b < nact; b++) {
+            // slots [0, nlog) of the workgroup's have a valid log
+            const int nlog = !DLOG ? 0 : (base != wg_slot0 ? nact : min(nact, max(B.dlog_valid - wg_slot0, 0)));
+            if constexpr (DLOG) {
+                // logged lines: a wave per (slot, table), so that the short logs' round trips run side by side; then, all
+                // threads together, what no table holds and the tables whose logs overflowed
+                const int nwaves = nthr >> 6;
+                for (int p = wave; p < nlog * NCH; p += nwaves) {
+                    const int b = p / NCH, c = p - b * NCH;
+                    const u32 *lg = dlog_table(B, wg_slot0 + b, c, NCH);
+                    const u32 cnt = lg[0];
+                    if (cnt < B.dlog_cap)
+                        dlog_zero_lines(B.slots + (u64)(wg_slot0 + b) * M.slot_bytes + M.comp[c].ht_off, M.comp[c].ht_len, lg, cnt, lane, 64);
+                }
+                for (int b = 0; b < nlog; b++) {
+                    u8 *bs = B.slots + (u64)(wg_slot0 + b) * M.slot_bytes;
+                    dlog_zero_rest(M, bs, NCH, tid, nthr);
+                    for (int c = 0; c < NCH; c++) {
+                        if (dlog_table(B, wg_slot0 + b, c, NCH)[0] >= B.dlog_cap)
+                            dlog_zero_range(bs, M.comp[c].ht_off, M.comp[c].ht_off + M.comp[c].ht_len, tid, nthr);
+                    }
+                }
+            }
+            for (int b = nlog; b < nact; b++) {
                 uint4 *z4 = reinterpret_cast<uint4 *>(B.slots + (u64)(wg_slot0 + b) * M.slot_bytes);
                 for (u64 i = tid; i < n16; i += nthr) z4[i] = zero;
             }
@@ -988,9 +1043,9 @@ __global__ void __launch_bounds__(64 * (NCH + (MIXT ? 2 : 1))) k_pipe(const DBat
 
         Coder X;
         X.low = 1; X.high = 0xFFFFFFFFu; X.opos = 0; X.cap = S.cap; X.dst = S.dst;
-        if (wave == 0) comp_loop<NCH, SP, HIO, true, false, false, KEEP>(S);
-        else if (wave < NCH - 1) comp_loop<NCH, SP, HIO, false, false, false, KEEP>(S);
-        else if (wave == NCH - 1) comp_loop<NCH, SP, HIO, false, !MIXT, MIXT, KEEP>(S);
+        if (wave == 0) comp_loop<NCH, SP, HIO, true, false, false, KEEP, DLOG>(S);
+        else if (wave < NCH - 1) comp_loop<NCH, SP, HIO, false, false, false, KEEP, DLOG>(S);
+        else if (wave == NCH - 1) comp_loop<NCH, SP, HIO, false, !MIXT, MIXT, KEEP, DLOG>(S);
         else if (MIXT && wave == NCH) mix_loop<NCH, HIO, KEEP>(S);
         else coder_loop<NST, HIO>(S, X);
         __syncthreads();
@@ -1025,6 +1080,7 @@ __global__ void __launch_bounds__(64 * (NCH + (MIXT ? 2 : 1))) k_pipe(const DBat
         __syncthreads();
     }
 }
+
 
 // The encoder of the dense short chains (levels 1-2) with every stage split into a history wave and a counter / weights
 // wave (hist_loop / pred_loop): 2 * NCH + 1 waves.  Wave -> role, chosen for the SIMD a wave lands on (wave w runs on SIMD
@@ -1163,6 +1219,16 @@ __global__ void __launch_bounds__(64 * (2 * NCH + 1)) k_pipe2(const DBatch B, co
 
 }  // namespace zpqp
 
+#ifdef ZPQ_PIPE_LOG_TU
+// ------------------------------------------------------------------ zpq_pipe_log.hip: the one kernel of this unit and its launch
+extern "C" int zpq_launch_lpipe(const DBatch *B, const zpqc::Cfg *cfg, const void *layout, int nwg, size_t lds, hipStream_t stream)
+{
+    const zpqp::PipeLds &L = *static_cast<const zpqp::PipeLds *>(layout);
+    (void)hipFuncSetAttribute((const void *)zpqp::k_lpipe<3, false, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL((zpqp::k_lpipe<3, false, false, false, false, true>), dim3(nwg), dim3(64 * 4), lds, stream, *B, *cfg, L);
+    return ZPQ_OK;
+}
+#else
 // ------------------------------------------------------------------ host side
 using zpqc::Cfg;
 
@@ -1209,6 +1275,18 @@ extern "C" int zpq_pipe_applies(const DModel *M, int blocks_per_wg, int nslots)
     zpqp::PipeLds L;
     size_t lds = 0;
     return pipe_layout(cfg, blocks_per_wg, &L, &lds) ? 1 : 0;
+}
+
+// Would zpq_launch_pipe run this batch on the kernel that keeps the dirty-line log?  The dense chain of three (level 2) on
+// unsplit k_pipe, no striped upload, no block set.  (k_pipe2, the line store, the other chain lengths and the KEEP and HIO
+// forms keep no log: a launch of theirs leaves the pool's logs invalid.)
+extern "C" int zpq_pipe_keeps_dlog(const DBatch *B, const DModel *hostM, int blocks_per_wg)
+{
+    if (B->gate_flag || (B->flags & ZB_KEEP_STATE) || !zpq_pipe_applies(hostM, blocks_per_wg, B->nslots)) return 0;
+    Cfg cfg;
+    if (!zpq_chain_build_cfg(hostM, &cfg) || cfg.sparse || cfg.has_mix2 || cfg.nch_spec != 3) return 0;
+    const char *ev = getenv("ZPQ_ENC_SPLIT");             // (a wave order asks for k_pipe2: zpq_launch_pipe)
+    return !(ev && strlen(ev) >= 4) ? 1 : 0;
 }
 
 // A wave -> role order for k_pipe2 is usable when every component c < nch is there exactly once, either whole (8 + c) or as
@@ -1263,6 +1341,7 @@ extern "C" int zpq_launch_pipe(const DBatch *B, const DModel *hostM, int nwg, in
     // a block set's launch (ZPQ_SET_PIPE): k_pipe<..., KEEP>, block i on slot slot_map[i], one block per slot and launch
     const bool keep = (B->flags & ZB_KEEP_STATE) != 0;
     if (keep && (hio || !B->slot_map || B->nslots != B->nblocks)) return ZPQ_E_INTERNAL;
+    if (B->dlog && !zpq_pipe_keeps_dlog(B, hostM, blocks_per_wg)) return ZPQ_E_INTERNAL;   // (the host offers the log to the kernel that keeps it)
     // Dense level 1: every stage split into a history wave and a counter / weights wave (k_pipe2): 136 -> 101 ms for 4096
     // blocks.  Level 2 has seven such roles for four SIMDs; every order and every mix of split and whole stages that was
     // tried ran at 122-137 ms against 123 for k_pipe (two waves sharing a SIMD issue slower together than the instruction
@@ -1335,6 +1414,9 @@ extern "C" int zpq_launch_pipe(const DBatch *B, const DModel *hostM, int nwg, in
         }
         return ZPQ_OK;
     }
+    if (B->dlog) {                                          // (the dense chain of three: zpq_pipe_keeps_dlog)
+        return zpq_launch_lpipe(B, &cfg, &L, nwg, lds, stream);   // k_lpipe (zpq_pipe_log.hip)
+    }
     switch (cfg.nch_spec) {
     case 2: if (cfg.sparse) ZPP_LAUNCH(2, false, true, false); else if (hio) ZPP_LAUNCH(2, false, false, true); else ZPP_LAUNCH(2, false, false, false); break;
     case 3: if (cfg.sparse) ZPP_LAUNCH(3, false, true, false); else if (hio) ZPP_LAUNCH(3, false, false, true); else ZPP_LAUNCH(3, false, false, false); break;
@@ -1347,3 +1429,4 @@ extern "C" int zpq_launch_pipe(const DBatch *B, const DModel *hostM, int nwg, in
 #undef ZPP_LAUNCH_K
     return ZPQ_OK;
 }
+#endif   // ZPQ_PIPE_LOG_TU
