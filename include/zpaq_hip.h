@@ -477,6 +477,9 @@ int zpq_debug_contexts(zpq_ctx *, const zpq_model *, const uint8_t *in, size_t n
  * words left in the part of them a launch expects zeroed: 0 when the logs name every dirty line.  ZPQ_E_ARG unless the
  * last launches on the pool left valid logs for at least nslots slots. */
 int zpq_debug_pool_residue(zpq_ctx *, int nslots, uint64_t *count);
+/* The logs' counts as the last launch left them: counts[3 * slot + table] for the pool's first nslots slots (a count equal
+ * to the capacity = the log overflowed).  A copy and nothing else: no kernel, nothing cleared.  ZPQ_E_ARG as above. */
+int zpq_debug_dlog_counts(zpq_ctx *, int nslots, uint32_t *counts /* nslots * 3 */);
 /* Encode one fresh block with the generic kernel and record predict()'s return
  * value for the first ntrace modelled bits (predictor.v:536-668). */
 int zpq_debug_encode_trace(zpq_ctx *, const zpq_model *, const uint8_t *in, size_t n,

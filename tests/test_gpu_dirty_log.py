@@ -4,129 +4,11 @@ of every slot.  A line that was dirtied and not logged, or logged and not cleare
 sequences below put a block whose result depends on clean tables behind one that dirtied them, on one ctx, and compare every
 launch with the C oracle stream for stream.  Each sequence runs twice per log capacity: once as it is (the kernels' own
 clear), once with zpq_debug_pool_residue after every launch that keeps the log (it must find nothing left)."""
-import random
-
 import pytest
 
-import oracle_lib as O
+from dirty_log import Run
 
 pytestmark = pytest.mark.gpu
-
-WORDS = [b"the", b"of", b"block", b"line", b"table", b"state", b"and", b"zero", b"log", b"clear", b"count", b"a", b"in", b"row"]
-
-
-def small_table_header(bits):
-    """Level 2's header with every hash table shrunk to 64 << bits bytes: a block's contexts alias in a few lines."""
-    h = bytearray(O.level_header(2))
-    sz = [0, 2, 3, 2, 3, 4, 6, 6, 3, 5]
-    p = 5
-    for _ in range(h[4]):
-        if h[p] in (3, 8):
-            h[p + 1] = bits
-        p += sz[h[p]]
-    return bytes(h)
-
-
-HEADERS = {"level2": O.level_header(2), "small": small_table_header(4)}
-
-
-def make(kind, seed, n):
-    rnd = random.Random(seed)
-    if kind == "uniform":
-        return bytes(rnd.getrandbits(8) for _ in range(n))
-    if kind == "zeros":
-        return bytes(n)
-    if kind == "text":
-        out = bytearray()
-        while len(out) < n:
-            out += rnd.choice(WORDS) + b" "
-        return bytes(out[:n])
-    p = 19 + seed % 50                                    # periodic
-    unit = bytes(rnd.getrandbits(8) for _ in range(p))
-    return (unit * (n // p + 1))[:n]
-
-
-def batch(kind, nb, seed):
-    """nb ragged blocks of 1-8 KiB (and an empty and a one-byte one where there is room for them)."""
-    rnd = random.Random(1000 * seed + nb)
-    lens = [rnd.choice([1024, 1025, 1531, 2048, 3000, 4099, 6000, 8192]) for _ in range(nb)]
-    if nb >= 16:
-        lens[3], lens[7] = 0, 1
-    return [make(kind, 100 * seed + i, n) for i, n in enumerate(lens)]
-
-
-_want = {}
-
-
-def oracle(name, kind, nb, seed, pp):
-    key = (name, kind, nb, seed, pp)
-    if key not in _want:
-        blocks = batch(kind, nb, seed)
-        _want[key] = (blocks, O.encode_blocks(HEADERS[name], blocks, pp=pp, nthreads=8))
-    return _want[key]
-
-
-class Run:
-    def __init__(self, zpq, ctx, name, cap_env, residue):
-        self.zpq, self.ctx, self.name, self.residue = zpq, ctx, name, residue
-        self.model = zpq.Model(header=HEADERS[name])
-        self.on = cap_env != "0"
-
-    def after(self, keeps):
-        """keeps: the launch was one of the two kernels that keep the log"""
-        if not self.residue:
-            return
-        n = self.ctx.last_slots
-        if keeps and self.on:
-            assert self.ctx.debug_pool_residue(n) == 0
-        else:
-            with pytest.raises(self.zpq.ZpqError):       # any other launch leaves no valid log
-                self.ctx.debug_pool_residue(n)
-
-    def enc(self, kind, nb, seed, pp=True, cap=None):
-        blocks, want = oracle(self.name, kind, nb, seed, pp)
-        coded, status, _ = self.ctx.encode_blocks(self.model, blocks, flags=self.zpq.FLAG_PP if pp else 0, cap=cap)
-        assert self.ctx.last_kernel_name == ("k_pipe<encode>" if nb >= 12 else "k_chain<encode>")
-        self.after(nb >= 12)
-        if cap is None:
-            assert (status == 0).all() and coded == want, (kind, nb)
-        else:
-            fits = [len(w) <= cap for w in want]
-            assert [s == 0 for s in status] == fits and not all(fits)
-            assert all(c == w for c, w, f in zip(coded, want, fits) if f)
-
-    def dec(self, kind, nb, seed, pp=True, cap=8200):
-        blocks, want = oracle(self.name, kind, nb, seed, pp)
-        back, status, *_ = self.ctx.decode_blocks(self.model, want, cap=cap, flags=self.zpq.FLAG_PP if pp else 0)
-        assert self.ctx.last_kernel_name == "k_chain<decode>"
-        self.after(True)
-        fits = [len(b) <= cap for b in blocks]
-        assert [s == 0 for s in status] == fits
-        assert all(b == w for b, w, f in zip(back, blocks, fits) if f), (kind, nb)
-
-    def both(self, kind, nb, seed, pp=True):
-        self.enc(kind, nb, seed, pp)
-        self.dec(kind, nb, seed, pp)
-
-    def other(self, level):
-        """a launch of another model on the pool: it keeps no log"""
-        m = self.zpq.Model(level=level)
-        blocks = batch("text", 16, level)
-        coded, status, _ = self.ctx.encode_blocks(m, blocks)
-        assert (status == 0).all()
-        self.after(False)
-        back, status, *_ = self.ctx.decode_blocks(m, coded, cap=8200)
-        assert (status == 0).all() and back == blocks
-        self.after(False)
-        m.close()
-
-    def blockset(self):
-        """a block set of the same model codes a segment per member between two pool launches"""
-        bs = self.zpq.BlockSet(self.ctx, self.model, 12)
-        segs = batch("uniform", 12, 77)
-        coded, status, _ = bs.encode_segments(segs)
-        assert (status == 0).all()
-        bs.close()
 
 
 def seq_classes(r):

@@ -148,6 +148,8 @@ def lib():
     L.zpq_debug_encode_trace.argtypes = [vp, vp, u8p, C.c_size_t, u32, vp, C.c_size_t, vp, vp, C.c_size_t]
     if hasattr(L, "zpq_debug_pool_residue"):               # (a ZPQ_LIB_PATH build from before the dirty-line log lacks it)
         L.zpq_debug_pool_residue.argtypes = [vp, i32, vp]
+    if hasattr(L, "zpq_debug_dlog_counts"):
+        L.zpq_debug_dlog_counts.argtypes = [vp, i32, vp]
     L.zpq_status_string.argtypes = [i32]
     L.zpq_status_string.restype = C.c_char_p
     L.zpq_version.restype = C.c_char_p
@@ -458,6 +460,13 @@ class Context:
         count = C.c_uint64(0)
         _ck(lib().zpq_debug_pool_residue(self.h, nslots, C.byref(count)), "zpq_debug_pool_residue")
         return int(count.value)
+
+    def debug_dlog_counts(self, nslots):
+        """The dirty-line logs' counts of the pool's first `nslots` slots, [nslots, 3], as the last launch left them (nothing
+        is cleared).  ZpqError unless the last launches left valid logs for that many slots."""
+        counts = np.zeros((nslots, 3), dtype=np.uint32)
+        _ck(lib().zpq_debug_dlog_counts(self.h, nslots, counts.ctypes.data), "zpq_debug_dlog_counts")
+        return counts
 
     def debug_contexts(self, model, data):
         n = model.ncomp

@@ -783,6 +783,21 @@ extern "C" int zpq_debug_pool_residue(zpq_ctx *c, int nslots, uint64_t *count) t
     return ZPQ_OK;
 } ZPQ_CATCH(return ZPQ_E_INTERNAL)
 
+// debug (tests): the counts (word 0) of the logs of the pool's first nslots slots, three per slot, as the last launch left
+// them: a strided copy and nothing else -- no kernel, nothing cleared, dlog_valid as it was.  ZPQ_E_ARG unless that many
+// slots hold valid logs.
+extern "C" int zpq_debug_dlog_counts(zpq_ctx *c, int nslots, uint32_t *counts) try
+{
+    if (!ctx_live(c) || !counts || nslots < 1) return ZPQ_E_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (nslots > c->dlog_valid || !c->dlog_model || !c->dlog.p) return ZPQ_E_ARG;
+    HIPCK(hipSetDevice(c->device));
+    const size_t pitch = (size_t)zpqdev::dlog_stride(c->dlog_cap) * 4;
+    HIPCK(hipMemcpy2DAsync(counts, 4, c->dlog.p, pitch, 4, (size_t)nslots * 3, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return ZPQ_OK;
+} ZPQ_CATCH(return ZPQ_E_INTERNAL)
+
 extern "C" int zpq_encode_blocks_dev(zpq_ctx *c, const zpq_model *m, int nblocks, const uint8_t *in,
                                      const uint64_t *in_off, uint32_t flags, uint8_t *out,
                                      const uint64_t *out_off, uint32_t *out_len, int32_t *status) try
